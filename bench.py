@@ -1,6 +1,16 @@
 """Benchmark of the per-pixel ray-tracing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config K3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config K3] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit,
+ms_per_step (the milliseconds one timed step took), the configuration, the timed breakdown
+and the gather.  --dump-outputs DIR then writes the image the last timed step left (what a
+caller of the timed path receives) as DIR/image.npy, float32; scene, camera and per-frame
+seeds are fixed, so two builds run with the same arguments can be compared pixel for pixel.
+--full adds everything that takes work of its own and is described below: the fixture checks
+(image_ok, share_ok), segments_per_s, the roofline (a repetition of the timed call), the
+side measurements and the CPU baseline.
 
 Configs (BASELINE.json `configs`):
   K2, K3 (default)  1920x1080, 3 / 500 spheres, max_depth 1.  A step is ONE progressive
@@ -141,6 +151,14 @@ def parse(argv=None):
                     help="frames for each side measurement (0 = none)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="CPU baseline budget in seconds (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the fixture checks (image_ok, "
+                         "share_ok), the roofline's repetition of the timed call, the side "
+                         "measurements (--side) and the CPU baseline (--cpu-seconds); without "
+                         "it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the image after the "
+                         "last step, rank 0) as DIR/image.npy, float32")
     a = ap.parse_args(argv)
     d_steps, d_warm = DEFAULT_STEPS[a.config]
     a.steps = d_steps if a.steps is None else a.steps
@@ -279,6 +297,27 @@ def canon_sha(a) -> str:
     a = np.ascontiguousarray(a, np.float32).copy()
     a.view(np.uint32)[np.isnan(a)] = CANON_NAN
     return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0x0D0C
+
+
+def dump_outputs(directory, image):
+    """--dump-outputs: what the timed steps computed, as a caller receives it — the RGBA32F
+    image after the last step ([H, W, 4], the gathered one at N > 1) — written as
+    DIR/image.npy in float32.  An image above DUMP_MAX_BYTES (K5) is written as a fixed,
+    seeded sample of its pixels instead ([P, 4], in ascending pixel order)."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    img = np.ascontiguousarray(image.detach().cpu().numpy(), np.float32)
+    if img.nbytes > DUMP_MAX_BYTES:
+        px = img.reshape(-1, 4)
+        keep = DUMP_MAX_BYTES // 2 // 16
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+            px.shape[0], size=keep, replace=False))
+        img = np.ascontiguousarray(px[pick])
+    np.save(out / "image.npy", img)
 
 
 def _fixture(config):
@@ -870,7 +909,7 @@ def main(argv=None):
     # path costs ≈ 9 µs more per call, so it never runs inside the region), one-launch-per-
     # frame steps (which carry none) between HIP events
     launch_timing = launch_mode != "dispatch"
-    rep = StripeRenderer(pipe, w, h, rank, world, comm=None)
+    rep = StripeRenderer(pipe, w, h, rank, world, comm=None) if args.full else None
 
     def run():
         if gate:
@@ -888,7 +927,9 @@ def main(argv=None):
                      stamp=stamp if host_t is not None else None)
     dt = ts["dt"]
     info = pipe.last_launch_info()             # the last timed rt_update_frames call
-    if launch_timing:
+    if not args.full:
+        pass                                   # the roofline's repetition: --full only
+    elif launch_timing:
         # the repetition's last call: all K steps (K2/K3 chains) or one 64-spp step
         if dispatch:
             step_block(rep, args.warmup, True)
@@ -932,55 +973,68 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         gather_s, dt_gather = (float(x) for x in t.tolist())
     frames_total = (args.warmup + args.steps) if dispatch else spf
-    image_ok, image_what = image_check(cfg, image, frames_total, cam0)
-    share_ok = share_check(cfg, r.local, frames_total, stripe_bands(h, rank, world))
-    if world > 1:
-        flag = torch.tensor([{True: 1, False: 0, None: 2}[share_ok]], dtype=torch.int32,
-                            device=red_dev)
-        got = [torch.zeros_like(flag) for _ in range(world)]
-        dist.all_gather(got, flag)
-        vals = [int(g[0]) for g in got]
-        share_ok = None if 2 in vals else all(v == 1 for v in vals)
-    cand_stats = pipe.candidate_stats()
-
-    total_launches = info["launches"] * (1 if dispatch else args.steps)
-    launches_per_step = total_launches / args.steps
-    queues = max(1, info.get("queues", 1))
-    if launch_timing:
-        launch_s = k_s / max(1, k_launches)
-    else:
-        launch_s = rep_s / max(1, total_launches // queues)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image)
     value = w * h * spf * args.steps / dt / 1e6
-
     kernel = info["kernel_name"]
-    fpl = info["max_frames_per_launch"]
-    if launch_mode == "chain":
-        # a frame chain carries fpl progressive updates, the accumulator in registers between
-        # them: it reads the input once (16 B per pixel) and writes every frame's image (16 B
-        # per pixel per frame)
-        bytes_launch = local_px * (16 * fpl + 16)
-    elif dispatch:
-        bytes_launch = local_px * BYTES_PER_PIXEL_LAUNCH
-    else:
-        # 64-spp steps: one read and the last two frames' images per launch
-        bytes_launch = local_px * 16 * 3
-    pmc, pmc_path = load_pmc(cfg, kernel, fpl, queues) if world == 1 else (None, None)
-    pq = pmc.get("queues", 1) if pmc else 1
-    ref_bytes = local_px * BYTES_PER_PIXEL_LAUNCH * fpl   # the reference: one dispatch per frame
-    wgt = load_weighted(cfg, kernel, pmc_path) if pmc else (None, None)
-    roof = roofline(kernel, launch_s, bytes_launch, pmc, pmc_path, pq, ref_bytes=ref_bytes,
-                    weighted=wgt if wgt[0] else None,
-                    extra={"frames_per_launch": fpl, "launches_per_step": launches_per_step,
-                           "queues": queues, "submit": info.get("submit"),
-                           "kernel_time": kernel_how})
 
-    segs = fixture_segments(cfg, frames_total)
-    if dispatch and depth == 1:
-        seg_step = w * h            # one sphere_list_hit per camera ray at max_depth 1
-    elif segs:
-        seg_step = segs             # one step = the fixture's 64-spp render
-    else:
-        seg_step = None
+    def checks_and_roofline():
+        """--full: the fixture checks, the roofline of the timed kernel, segments/s and the
+        candidate lists' statistics, as fields of the line."""
+        image_ok, image_what = image_check(cfg, image, frames_total, cam0)
+        share_ok = share_check(cfg, r.local, frames_total, stripe_bands(h, rank, world))
+        if world > 1:
+            flag = torch.tensor([{True: 1, False: 0, None: 2}[share_ok]], dtype=torch.int32,
+                                device=red_dev)
+            got = [torch.zeros_like(flag) for _ in range(world)]
+            dist.all_gather(got, flag)
+            vals = [int(g[0]) for g in got]
+            share_ok = None if 2 in vals else all(v == 1 for v in vals)
+        cand_stats = pipe.candidate_stats()
+
+        total_launches = info["launches"] * (1 if dispatch else args.steps)
+        launches_per_step = total_launches / args.steps
+        queues = max(1, info.get("queues", 1))
+        if launch_timing:
+            launch_s = k_s / max(1, k_launches)
+        else:
+            launch_s = rep_s / max(1, total_launches // queues)
+
+        fpl = info["max_frames_per_launch"]
+        if launch_mode == "chain":
+            # a frame chain carries fpl progressive updates, the accumulator in registers
+            # between them: it reads the input once (16 B per pixel) and writes every frame's
+            # image (16 B per pixel per frame)
+            bytes_launch = local_px * (16 * fpl + 16)
+        elif dispatch:
+            bytes_launch = local_px * BYTES_PER_PIXEL_LAUNCH
+        else:
+            # 64-spp steps: one read and the last two frames' images per launch
+            bytes_launch = local_px * 16 * 3
+        pmc, pmc_path = load_pmc(cfg, kernel, fpl, queues) if world == 1 else (None, None)
+        pq = pmc.get("queues", 1) if pmc else 1
+        ref_bytes = local_px * BYTES_PER_PIXEL_LAUNCH * fpl   # the reference: a dispatch per frame
+        wgt = load_weighted(cfg, kernel, pmc_path) if pmc else (None, None)
+        roof = roofline(kernel, launch_s, bytes_launch, pmc, pmc_path, pq, ref_bytes=ref_bytes,
+                        weighted=wgt if wgt[0] else None,
+                        extra={"frames_per_launch": fpl, "launches_per_step": launches_per_step,
+                               "queues": queues, "submit": info.get("submit"),
+                               "kernel_time": kernel_how})
+
+        segs = fixture_segments(cfg, frames_total)
+        if dispatch and depth == 1:
+            seg_step = w * h            # one sphere_list_hit per camera ray at max_depth 1
+        elif segs:
+            seg_step = segs             # one step = the fixture's 64-spp render
+        else:
+            seg_step = None
+        return {"roofline": roof,
+                "segments_per_s": (round(seg_step * args.steps / dt, 1) if seg_step else None),
+                "image_ok": image_ok,
+                "image_check": image_what,
+                "share_ok": share_ok,
+                "candidate_lists": cand_stats}
+
     line = {
         "metric": BASELINE["metric"],
         "value": round(value, 2),
@@ -1007,11 +1061,7 @@ def main(argv=None):
                                          "chain": "the K steps' frames in fused launches, every "
                                                   "frame's image written",
                                          None: "64 frames per step"}[launch_mode])},
-        "roofline": roof,
-        "segments_per_s": (round(seg_step * args.steps / dt, 1) if seg_step else None),
-        "image_ok": image_ok,
-        "image_check": image_what,
-        "share_ok": share_ok,
+        "full": args.full,
         "timed_breakdown_ms": {"job": round(dt * 1e3, 4),
                                "max_rank": round(ts["max_rank_s"] * 1e3, 4),
                                "per_rank_ms": [round(x * 1e3, 4) for x in ts["per_rank"]],
@@ -1024,15 +1074,18 @@ def main(argv=None):
         "job": {"wall_ms": round((dt + dt_gather) * 1e3, 4),
                 "Mrays_per_s": round(w * h * spf * args.steps / (dt + dt_gather) / 1e6, 2),
                 "what": "the K steps plus the one gather of the finished tiles"},
-        "candidate_lists": cand_stats,
         "warm_up": {"ms": round(warm_s * 1e3, 2), "steps": args.warmup},
     }
+    if args.dump_outputs:
+        line["outputs"] = args.dump_outputs
+    if args.full:
+        line.update(checks_and_roofline())
     if host_t is not None:
         line["timeline_host"] = host_t
 
-    # ---- side measurements (after the timed region and its image check) -------------
+    # ---- side measurements (--full; after the timed region and its image check) ------
     side = {}
-    if args.side > 0 and world == 1:
+    if args.full and args.side > 0 and world == 1:
         base = args.warmup + args.steps
         if dispatch and depth == 1:
             # the reference algorithm (exhaustive scan) on further frames: its FP32 roofline
@@ -1092,7 +1145,7 @@ def main(argv=None):
     line.update(side)
 
     if rank == 0:
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(cam0, spheres, w, h, args.cpu_seconds)
         print(json.dumps(line, default=_unserializable), flush=True)
     if comm is not None:

@@ -53,6 +53,38 @@ def test_one_launch_structure_at_every_n(bench):
     assert not hasattr(bench, "frame_launch_mode")
 
 
+def test_plain_run_by_default_full_on_request(bench):
+    """A plain run does only the timed steps: the checks, the roofline's repetition, the side
+    lines and the CPU baseline are behind --full; --steps sets the timed steps."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_image_or_fixed_sample(bench, tmp_path):
+    """--dump-outputs writes DIR/image.npy in float32: the image itself up to DUMP_MAX_BYTES,
+    above it the same seeded sample of its pixels on every run, in pixel order."""
+    import numpy as np
+    import torch
+    img = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    bench.dump_outputs(tmp_path / "a", img)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.numpy())
+    h, w = 1024, 1024                         # 16 MiB + one row: just above the cap set below
+    big = torch.arange((h + 1) * w, dtype=torch.float32).reshape(h + 1, w, 1).expand(h + 1, w, 4)
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = h * w * 16
+    try:
+        bench.dump_outputs(tmp_path / "b", big)
+        bench.dump_outputs(tmp_path / "c", big)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert b.dtype == np.float32 and b.shape == (h * w // 2, 4) and np.array_equal(b, c)
+    assert (np.diff(b[:, 0]) > 0).all() and (b[:, 0] == b[:, 3]).all()
+
+
 def test_stripe_bands_round_robin(bench):
     assert bench.stripe_bands(1080, 0, 8)[:3] == [0, 8, 16]
     assert bench.stripe_bands(1080, 7, 8)[-1] == 127

@@ -10,7 +10,7 @@ export RT_BENCH_BACKEND=gloo
 run() {  # nproc port args...
   local n=$1 port=$2; shift 2
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n "$@" --cpu-seconds 0
+    --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n "$@" --full --cpu-seconds 0
 }
 run 2 29511 --steps 20 --warmup 5 > $O/k3_n2_driver.json 2> $O/k3_n2_driver.err || { tail $O/k3_n2_driver.err; exit 1; }
 run 3 29512 --side 0 > $O/k3_n3.json 2> $O/k3_n3.err || { tail $O/k3_n3.err; exit 1; }

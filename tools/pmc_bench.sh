@@ -15,7 +15,7 @@ TAG=$1; CFGS=$2; PMC_ROUND=${PMC_ROUND:-r06}; QUEUES=${QUEUES:-0}
 cd $GRAFT_REPO_ROOT; O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 for c in $CFGS; do
-  ARGS="--config $c --side 0 --cpu-seconds 0 --queues $QUEUES"
+  ARGS="--config $c --full --side 0 --cpu-seconds 0 --queues $QUEUES"   # --full: the roofline fields
   [ "$c" = "K5" ] && ARGS="$ARGS --steps 1 --warmup 1"
   { [ "$c" = "K3" ] || [ "$c" = "K2" ]; } && ARGS="$ARGS --steps 20 --warmup 5"
   timeout -k 10 300 python3 bench.py $ARGS > $O/pmc_bench_$c.json 2> $O/pmc_bench_$c.err \

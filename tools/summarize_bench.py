@@ -1,4 +1,5 @@
-"""Prints the headline fields of a bench.py JSON line (its last line starting with '{').
+"""Prints the headline fields of a bench.py --full JSON line (its last line starting with
+'{'; a plain run's line has no roofline or image check to summarize).
 usage: python tools/summarize_bench.py LINE.json"""
 import json
 import sys
