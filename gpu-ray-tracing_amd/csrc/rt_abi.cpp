@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_chain_parts.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -79,8 +80,11 @@ struct rt_ctx {
     // Cost-ordered tiles (TraceParams::tile_order): per-tile durations recorded by the
     // first camera-ray-only launch of a list generation, and the order derived from them.
     uint32_t* tile_cost = nullptr;
+    // order_tiles entries, then the same order dealt into the two chain parts' sub-lists
+    // (rt_set_chain_parts), then the raster order dealt the same way (chain_raster_key)
     uint32_t* tile_order = nullptr;
     uint64_t order_tiles = 0;       // allocated tiles
+    uint64_t chain_raster_key[2] = {0, 0};   // units, units per band row of the raster table
     uint64_t cost_gen = ~0ull;      // cand_gen tile_cost was measured for
     uint32_t cost_frames = 0;       // frames of the launch that measured it
     uint64_t order_gen = ~0ull;     // cand_gen tile_order was derived for
@@ -107,13 +111,16 @@ struct rt_ctx {
     };
     std::vector<CountRecord> counts;
     uint32_t frames_per_launch = 0;  // rt_update_frames fusion cap (0 = automatic)
-    rt_launch_info last = {0, 0, 0, -1, 0, 0, 0};  // the last call's launches (rt_last_launch_info)
+    rt_launch_info last = {0, 0, 0, -1, 0, 0, 0, 1};  // the last call's launches (rt_last_launch_info)
     int path_compaction = RT_PATHS_AUTO;
     int frame_pairs = RT_FRAME_PAIRS_AUTO;
     int single_kernel = RT_SINGLE_AUTO;
     // Concurrent parts of one-frame updates (rt_set_update_queues): part 0 on the caller's
     // stream, part k on aux[k - 1], forked and joined through events.
     uint32_t update_queues = 0;      // 0 = automatic
+    // Two staggered parts of a call's fused frame-group launches (rt_set_chain_parts): part 0
+    // on the caller's stream, part 1 on aux[0]
+    uint32_t chain_parts = 0;        // 0 = automatic
     hipStream_t aux[RT_MAX_UPDATE_QUEUES - 1] = {};
     hipEvent_t fork_ev = nullptr;
     hipEvent_t join_ev[RT_MAX_UPDATE_QUEUES - 1] = {};
@@ -672,6 +679,25 @@ rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t stream
 // that the cheap ones fill the tail.  The sort runs only when a generation is reused, so a
 // camera that moves every call never pays for it.  Only the workgroup -> tile assignment
 // changes, never a pixel's result.
+rt_status ensure_order_buffers(rt_ctx* ctx, uint64_t tiles, hipStream_t stream) {
+    if (tiles <= ctx->order_tiles) return RT_OK;
+    if (ctx->order_tiles) {
+        hipError_t e = hipStreamSynchronize(stream);   // old order may be in use
+        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    }
+    (void)hipFree(ctx->tile_cost);
+    (void)hipFree(ctx->tile_order);
+    ctx->tile_cost = ctx->tile_order = nullptr;
+    ctx->order_tiles = 0;
+    ctx->cost_gen = ctx->order_gen = ~0ull;
+    ctx->chain_raster_key[0] = 0;
+    hipError_t e = hipMalloc(&ctx->tile_cost, tiles * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&ctx->tile_order, 3 * tiles * sizeof(uint32_t));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(tile order)");
+    ctx->order_tiles = tiles;
+    return RT_OK;
+}
+
 rt_status plan_tile_order(rt_ctx* ctx, rtk::TraceParams& p, int kernel, hipStream_t stream) {
     p.tile_order = nullptr;
     p.tile_cost = nullptr;
@@ -696,25 +722,12 @@ rt_status plan_tile_order(rt_ctx* ctx, rtk::TraceParams& p, int kernel, hipStrea
     const uint32_t tiles_x0 = (p.width + 7u) >> 3;
     const uint32_t tiles_x = (tiles_x0 + group - 1u) / group;
     const uint64_t tiles = (uint64_t)tiles_x * p.local_bands;
-    if (tiles > ctx->order_tiles) {
-        if (ctx->order_tiles) {
-            hipError_t e = hipStreamSynchronize(stream);   // old order may be in use
-            if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-        }
-        (void)hipFree(ctx->tile_cost);
-        (void)hipFree(ctx->tile_order);
-        ctx->tile_cost = ctx->tile_order = nullptr;
-        ctx->order_tiles = 0;
-        ctx->cost_gen = ctx->order_gen = ~0ull;
-        hipError_t e = hipMalloc(&ctx->tile_cost, tiles * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&ctx->tile_order, tiles * sizeof(uint32_t));
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(tile order)");
-        ctx->order_tiles = tiles;
-    }
+    if (rt_status s = ensure_order_buffers(ctx, tiles, stream)) return s;
     // the order from the newest measurement of this generation
     if (ctx->cost_gen == gen && (ctx->order_gen != gen || ctx->order_frames < ctx->cost_frames)) {
         hipError_t e = rtk::launch_tile_order(ctx->tile_cost, ctx->tile_order,
-                                              (uint32_t)tiles, tiles_x, stream);
+                                              (uint32_t)tiles, tiles_x, stream, 1u,
+                                              ctx->tile_order + ctx->order_tiles, 2u);
         if (e != hipSuccess) return hip_fail(e, "rt_tile_order_kernel launch");
         ctx->order_gen = gen;
         ctx->order_frames = ctx->cost_frames;
@@ -1331,7 +1344,7 @@ rt_status trace(rt_ctx* ctx, const float* in, float* out, uint32_t w, uint32_t h
         return s;
     const float4* src = reinterpret_cast<const float4*>(in);
     float4* dst = reinterpret_cast<float4*>(out);
-    ctx->last = {0, 0, 0, -1, 0, 0, 0};
+    ctx->last = {0, 0, 0, -1, 0, 0, 0, 1};
     for (uint32_t f0 = 0; f0 < frames; f0 += rtk::kMaxFramesPerLaunch) {
         const uint32_t nf = std::min<uint32_t>(frames - f0, rtk::kMaxFramesPerLaunch);
         p.in = src;
@@ -1614,6 +1627,134 @@ rt_status rt_render(rt_ctx* ctx, const float* in, float* out, uint32_t w, uint32
 
 namespace {
 
+// ---- chain parts (rt_set_chain_parts) ------------------------------------------------------
+// A call of several fused frame-group launches waits, between two launches, for the first to
+// drain: its last round of workgroups leaves SIMDs below their resident waves or idle.  The
+// frames of a chain depend on each other per pixel only, so the call's scheduling units are
+// dealt into two parts, each a chain of launches on its own stream, and the parts' launch
+// boundaries are staggered: one part drains while the other is in mid-launch.
+//
+// The schedule, a pure function of (frames, cap): part 0 cuts at multiples of cap, part 1 at
+// its first launch (cap / 2, or 3 cap / 4) + multiples of cap.  Variant kScheduleShortTails ends each part with a short launch
+// (cap / 4 and cap / 8 frames: the one drain nothing overlaps is that of the call's last
+// launches), variant kSchedulePlain does not.  No launch is above cap or, above a one-launch
+// call, below two frames (a one-frame launch is not a frame-group launch); no cut of one part
+// is a cut of the other.  frames <= cap, or cap < 4 (no stagger of two frames or more fits):
+// the unsplit chain, part 0 only.  Launches in issue order (by first frame, part 0 first).
+constexpr int kScheduleShortTails = 1, kSchedulePlain = 2;
+// further candidates: part 1 alone ends with a short launch (just under cap / 8, so that its
+// cut misses part 0's last); part 1's first launch is 3 cap / 4
+constexpr int kScheduleShortTail1 = 3, kScheduleLateStagger = 4, kScheduleVariants = 4;
+// Measured (plain bench.py, K3, 200 frames at cap 64, µs per frame, seven interleaved runs
+// each, profiles/chain_parts/ab_k3_200_schedules.jsonl): one chain 11.87 (11.85-11.92); short
+// tails 64/64/56/16 + 32/64/64/32/8 11.81 (11.71-11.95); plain 64/64/64/8 + 32/64/64/40 11.70
+// (11.62-11.75); part 1's short tail 64/64/64/8 + 32/64/64/34/6 11.69 (11.63-11.88); late
+// stagger 64/64/64/8 + 48/64/64/24 11.65 (11.62-11.70).  The kernel trace shows why the
+// tails do not pay: part 0, issued first, runs ahead (its launches get the larger share of
+// the machine), so part 1's last launch runs alone whatever its length, and every extra
+// launch costs its workgroups' start.  The late stagger leaves part 1 the shortest last launch
+// without an extra one.
+constexpr int kScheduleDefault = kScheduleLateStagger;
+
+void unsplit_schedule(uint32_t frames, uint32_t cap, std::vector<rt_chain_launch>& out) {
+    out.clear();
+    for (uint32_t f = 0; f < frames; f += cap) out.push_back({0u, f, std::min(cap, frames - f)});
+}
+
+// one part's launch lengths: `first`, then cap each, then (tail > 0) a last launch of `tail`
+bool part_lengths(uint32_t frames, uint32_t cap, uint32_t first, uint32_t tail,
+                  std::vector<uint32_t>& len) {
+    len.clear();
+    if (tail >= frames || first == 0) return false;
+    uint32_t body = frames - tail;
+    for (uint32_t n = std::min(first, body); body; n = std::min(cap, body)) {
+        len.push_back(n);
+        body -= n;
+    }
+    if (tail) len.push_back(tail);
+    // a one-frame last launch takes a frame from its predecessor; a one-frame launch before
+    // the tail joins the tail
+    const size_t k = len.size();
+    if (tail && k >= 2 && len[k - 2] == 1u) {
+        len[k - 1] += 1u;
+        len.erase(len.begin() + (long)(k - 2));
+    } else if (k >= 2 && len[k - 1] == 1u) {
+        len[k - 2] -= 1u;
+        len[k - 1] = 2u;
+    }
+    for (uint32_t n : len)
+        if (n < 2u || n > cap) return false;
+    return true;
+}
+
+bool staggered_schedule(uint32_t frames, uint32_t cap, int variant,
+                        std::vector<rt_chain_launch>& out) {
+    // per variant: part 1's first launch, and the parts' last (0: the remainder)
+    uint32_t first1 = cap / 2u, tail0 = 0u, tail1 = 0u;
+    if (variant == kScheduleShortTails) {
+        tail0 = std::max(2u, cap / 4u);
+        tail1 = std::max(2u, cap / 8u);
+    } else if (variant == kScheduleShortTail1) {
+        tail1 = cap >= 32u ? cap / 8u - 2u : 2u;
+    } else if (variant == kScheduleLateStagger) {
+        first1 = cap - cap / 4u;
+    }
+    std::vector<uint32_t> len[2];
+    if (!part_lengths(frames, cap, cap, tail0, len[0]) ||
+        !part_lengths(frames, cap, first1, tail1, len[1]))
+        return false;
+    if (len[0].size() < 2 || len[1].size() < 2) return false;
+    // cuts of part 0 and part 1, merged in issue order; a shared cut rejects the schedule
+    out.clear();
+    size_t i[2] = {0, 0};
+    uint32_t at[2] = {0, 0};
+    while (i[0] < len[0].size() || i[1] < len[1].size()) {
+        const int k = i[1] >= len[1].size() || (i[0] < len[0].size() && at[0] <= at[1]) ? 0 : 1;
+        if (at[0] == at[1] && at[0] != 0u) return false;
+        out.push_back({(uint32_t)k, at[k], len[k][i[k]]});
+        at[k] += len[k][i[k]++];
+    }
+    return at[0] == frames && at[1] == frames;
+}
+
+void chain_schedule(uint32_t frames, uint32_t cap, int variant, std::vector<rt_chain_launch>& out) {
+    cap = std::max(cap, 1u);
+    if (variant == 0) variant = kScheduleDefault;
+    if (frames > cap && cap >= 4u) {
+        if (staggered_schedule(frames, cap, variant, out)) return;
+        if (variant != kSchedulePlain && staggered_schedule(frames, cap, kSchedulePlain, out))
+            return;
+    }
+    unsplit_schedule(frames, cap, out);
+}
+
+// The frame-group instance of a launch whose every frame is hinted (rt_set_frame_pairs, not
+// OFF).  AUTO: four waves per tile when the share is small (a few tiles per SIMD), four per
+// pair of tiles up to twice that, two per pair above (rt_kernels.h kQuadMaxTiles /
+// kQuad2MaxTiles; DESIGN.md §5 "Frame groups over tile pairs").
+int frame_group_kernel(const rt_ctx* ctx, const rtk::TraceParams& p) {
+    const int mode = ctx->frame_pairs;
+    const uint64_t tiles = (uint64_t)((p.width + 7u) >> 3) * p.local_bands;
+    const bool automode = mode == RT_FRAME_PAIRS_AUTO;
+    // (the tile-pair instances read the candidate blocks: lists required)
+    const bool tpair = p.cand && (mode == RT_FRAME_PAIRS_ON2 || mode == RT_FRAME_PAIRS_QUAD2 ||
+                                  (automode && tiles > rtk::kQuadMaxTiles));
+    const bool quad = mode == RT_FRAME_PAIRS_QUAD || mode == RT_FRAME_PAIRS_QUAD2 ||
+                      (automode && (tiles <= rtk::kQuadMaxTiles ||
+                                    (tpair && tiles <= rtk::kQuad2MaxTiles)));
+    return quad ? (tpair ? rtk::kTraceListQuad2 : rtk::kTraceListQuad)
+                : (tpair ? rtk::kTraceListPair2 : rtk::kTraceListPair);
+}
+
+// AUTO's chain parts by tiles per launch.  Measured per size class (K3, 200-frame chain calls
+// that write every frame's image, rank 0's share at 1 / 2 / 4 / 8 ranks, µs per frame, one
+// chain against two parts, medians of three interleaved processes of five calls each,
+// profiles/chain_parts/rank_sim_cp*.jsonl): 32 400 tiles 11.89-11.97 against 11.58-11.65,
+// 16 320 tiles 6.24-6.33 against 6.09-6.14, 8 160 tiles 3.36-3.40 against 3.22-3.29, 4 080
+// tiles 2.09-2.12 against 1.99-2.04 — two parts in every class measured; smaller launches are
+// not measured and stay one chain.
+constexpr uint64_t kChainPartsMinTiles = 4000;
+
 rt_status update_frames(rt_ctx* ctx, float* image_a, float* image_b, uint32_t w, uint32_t h,
                         const rt_band_set& bands, const rt_scene_camera* cam,
                         const rt_sphere* spheres, uint32_t count, uint32_t frames,
@@ -1640,7 +1781,7 @@ rt_status update_frames(rt_ctx* ctx, float* image_a, float* image_b, uint32_t w,
     // instances run one frame per launch.
     const uint32_t per = frames_per_launch_for(ctx, p);
     int cur = 0;
-    ctx->last = {0, 0, 0, -1, 0, 0, 0};
+    ctx->last = {0, 0, 0, -1, 0, 0, 0, 1};
     // What the call has in flight beside the caller's stream, closed on every exit path (an
     // error return included): an AQL segment still being packed is dropped (nothing of it has
     // been submitted), and the context's aux streams are joined back into `stream`, so the
@@ -1676,6 +1817,139 @@ rt_status update_frames(rt_ctx* ctx, float* image_a, float* image_b, uint32_t w,
             if (ctx->timing) ctx->timed_launches = rtk::disarm_launch_events();
         }
     } timing_scope{ctx};
+    // Chain parts (rt_set_chain_parts): a call of two or more fused launches, every one a
+    // frame-group launch, as two staggered chains over disjoint halves of the scheduling units
+    // (chain_schedule).  With launch timing armed the call stays one chain: its kernel time is
+    // defined per sequential launch.
+    std::vector<rt_chain_launch> sched;
+    uint32_t n_in0 = 0;
+    const bool moved = cam->camera_has_moved > 0.5f;
+    // the share is of a class whose longer calls split (whatever this call's frames)
+    const bool chain_class =
+        ctx->chain_parts != 1u && per >= 4u && per <= rtk::kHintFrames &&
+        ctx->frame_pairs != RT_FRAME_PAIRS_OFF && trace_kernel_for(ctx, p) == rtk::kTraceList &&
+        (ctx->chain_parts == 2u ||
+         (uint64_t)((w + 7u) >> 3) * p.local_bands >= kChainPartsMinTiles);
+    if (chain_class && !ctx->aux[0]) {
+        // The first such call of the context — usually a short one, long before a call that
+        // splits — sets up what part 1 needs: the stream, the events, and the raster unit
+        // table, which part 1's stream builds here (forked from and joined into `stream`).
+        // The stream's hardware queue exists from this launch on; created by the first split
+        // call instead, it cost that call several milliseconds.
+        const int kernel = frame_group_kernel(ctx, p);
+        const uint32_t group =
+            kernel == rtk::kTraceListQuad2 || kernel == rtk::kTraceListPair2 ? 2u : 1u;
+        const uint32_t units_x = (((w + 7u) >> 3) + group - 1u) / group;
+        const uint64_t units = (uint64_t)units_x * p.local_bands;
+        if (rt_status s = ensure_aux_streams(ctx, 1u)) return s;
+        if (rt_status s = ensure_order_buffers(ctx, units, stream)) return s;
+        hipError_t e = hipEventRecord(ctx->fork_ev, stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0);
+        if (e != hipSuccess) return hip_fail(e, "fork (chain part set-up)");
+        fl.aux_live = 1u;
+        e = rtk::launch_raster_order(ctx->tile_order + 2 * ctx->order_tiles, (uint32_t)units,
+                                     units_x, 2u, ctx->aux[0]);
+        if (e != hipSuccess) return hip_fail(e, "rt_raster_order_kernel launch");
+        ctx->chain_raster_key[0] = units;
+        ctx->chain_raster_key[1] = units_x;
+        fl.aux_live = 0;
+        if (rt_status s = join_aux(ctx, 1u, stream)) return s;
+    }
+    if (chain_class && frames > per && !ctx->timing &&
+        (moved || lookup_count(ctx, img[0], p, n_in0))) {
+        int variant = 0;   // RT_CHAIN_SCHEDULE (environment, diagnostic): a schedule variant
+        if (const char* e = std::getenv("RT_CHAIN_SCHEDULE")) variant = std::atoi(e);
+        chain_schedule(frames, per, variant, sched);
+        if (std::none_of(sched.begin(), sched.end(),
+                         [](const rt_chain_launch& l) { return l.part != 0u; }))
+            sched.clear();   // no staggered schedule for this (frames, cap): one chain
+    }
+    if (!sched.empty()) {
+        const int kernel = frame_group_kernel(ctx, p);
+        const uint32_t group =
+            kernel == rtk::kTraceListQuad2 || kernel == rtk::kTraceListPair2 ? 2u : 1u;
+        const uint32_t units_x = (((w + 7u) >> 3) + group - 1u) / group;
+        const uint64_t units = (uint64_t)units_x * p.local_bands;
+        // The unit order is frozen for the call: the cost order when this generation has one
+        // (its dealt copy; the sort, if due, runs on `stream` here, before the fork), else the
+        // raster order dealt the same way.  Costs are recorded by the first launch of cap
+        // frames of each part (the same frames for every unit), when both parts have one.
+        p.frames = per;
+        p.store_each = ctx->frame_images == RT_FRAME_IMAGES_EVERY ? 2u : 1u;
+        if (rt_status s = plan_tile_order(ctx, p, kernel, stream)) return s;
+        if (rt_status s = ensure_order_buffers(ctx, units, stream)) return s;
+        const uint32_t* table = ctx->tile_order + ctx->order_tiles;
+        if (!p.tile_order) {
+            table = ctx->tile_order + 2 * ctx->order_tiles;
+            if (ctx->chain_raster_key[0] != units || ctx->chain_raster_key[1] != units_x) {
+                hipError_t e = rtk::launch_raster_order(ctx->tile_order + 2 * ctx->order_tiles,
+                                                        (uint32_t)units, units_x, 2u, stream);
+                if (e != hipSuccess) return hip_fail(e, "rt_raster_order_kernel launch");
+                ctx->chain_raster_key[0] = units;
+                ctx->chain_raster_key[1] = units_x;
+            }
+        }
+        uint32_t* const cost = p.tile_cost;
+        size_t rec[2] = {sched.size(), sched.size()};
+        for (size_t i = sched.size(); i-- > 0;)
+            if (sched[i].frames == per) rec[sched[i].part] = i;
+        const bool record = cost && rec[0] < sched.size() && rec[1] < sched.size();
+        // the count every pixel holds before frame f of the call
+        std::vector<uint32_t> n_at(frames + 1u);
+        n_at[0] = moved ? 0u : n_in0;
+        for (uint32_t f = 0; f < frames; ++f) n_at[f + 1u] = next_count(n_at[f], p.spp);
+        if (rt_status s = ensure_aux_streams(ctx, 1u)) return s;
+        // the fork, as the one-frame parts': no event when `stream` has nothing left to run
+        bool wait_fork = false;
+        if (hipStreamQuery(stream) != hipSuccess) {
+            hipError_t e = hipEventRecord(ctx->fork_ev, stream);
+            if (e != hipSuccess) return hip_fail(e, "fork (hipEventRecord)");
+            wait_fork = true;
+        }
+        p.parts = 2u;
+        for (size_t i = 0; i < sched.size(); ++i) {
+            const rt_chain_launch& L = sched[i];
+            // frame f of the call writes img[(1 + f) % 2], whichever launch carries it
+            p.part = L.part;
+            p.in = img[L.first & 1u];
+            p.out = img[1u - (L.first & 1u)];
+            p.out2 = img[L.first & 1u];
+            p.frames = L.frames;
+            p.reset_first = (L.first == 0u && moved) ? 1u : 0u;
+            for (uint32_t f = 0; f < L.frames; ++f)
+                p.seed_b[f] = host_f2u(seeds[L.first + f] * 4294967296.0f);
+            (void)fill_hint(p, n_at[L.first]);
+            if (p.hint_frames != L.frames)
+                return fail(RT_ERR_INVALID_ARGUMENT, "chain part launch is not fully hinted");
+            p.tile_order = table;
+            p.tile_cost = record && rec[L.part] == i ? cost : nullptr;
+            if (rt_status s = plan_split(ctx, p, kernel, stream)) return s;
+            if (rt_status s = plan_hint_rs(ctx, p, kernel)) return s;
+            if (L.part == 1u && wait_fork) {
+                hipError_t e = hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0);
+                if (e != hipSuccess) return hip_fail(e, "fork (hipStreamWaitEvent)");
+                wait_fork = false;
+            }
+            hipError_t e = rtk::launch_trace(p, kernel, L.part ? ctx->aux[0] : stream);
+            if (e != hipSuccess) return hip_fail(e, "frame-group launch (chain part)");
+            if (L.part) fl.aux_live = 1u;
+            note_launch(ctx, p, kernel, L.frames);
+            if (L.part) ctx->last.frames -= L.frames;   // (the call's frames, counted once)
+        }
+        ctx->last.chain_parts = 2u;
+        if (record) {
+            p.frames = per;
+            p.tile_cost = cost;
+            finish_tile_order(ctx, p);
+        }
+        fl.aux_live = 0;
+        if (rt_status s = join_aux(ctx, 1u, stream)) return s;
+        const int newest = (int)(frames & 1u);
+        record_count(ctx, img[newest], p, n_at[frames]);
+        record_count(ctx, img[1 - newest], p, n_at[frames - 1u]);
+        if (out_newest) *out_newest = newest;
+        return RT_OK;
+    }
     for (uint32_t f0 = 0; f0 < frames; f0 += per) {
         const uint32_t nf = std::min<uint32_t>(per, frames - f0);
         p.in = img[cur];
@@ -1705,22 +1979,7 @@ rt_status update_frames(rt_ctx* ctx, float* image_a, float* image_b, uint32_t w,
         int kernel = trace_kernel_for(ctx, p);
         const bool pairable = kernel == rtk::kTraceList && p.store_each && known &&
                               p.hint_frames == nf;
-        if (pairable && ctx->frame_pairs != RT_FRAME_PAIRS_OFF) {
-            // AUTO: four waves per tile when the share is small (a few tiles per SIMD), four
-            // per pair of tiles up to twice that, two per pair above (rt_kernels.h
-            // kQuadMaxTiles / kQuad2MaxTiles; DESIGN.md §5 "Frame groups over tile pairs")
-            const int mode = ctx->frame_pairs;
-            const uint64_t tiles = (uint64_t)((w + 7u) >> 3) * p.local_bands;
-            const bool automode = mode == RT_FRAME_PAIRS_AUTO;
-            // (the tile-pair instances read the candidate blocks: lists required)
-            const bool tpair = p.cand && (mode == RT_FRAME_PAIRS_ON2 || mode == RT_FRAME_PAIRS_QUAD2 ||
-                                          (automode && tiles > rtk::kQuadMaxTiles));
-            const bool quad = mode == RT_FRAME_PAIRS_QUAD || mode == RT_FRAME_PAIRS_QUAD2 ||
-                              (automode && (tiles <= rtk::kQuadMaxTiles ||
-                                            (tpair && tiles <= rtk::kQuad2MaxTiles)));
-            kernel = quad ? (tpair ? rtk::kTraceListQuad2 : rtk::kTraceListQuad)
-                          : (tpair ? rtk::kTraceListPair2 : rtk::kTraceListPair);
-        }
+        if (pairable && ctx->frame_pairs != RT_FRAME_PAIRS_OFF) kernel = frame_group_kernel(ctx, p);
         kernel = single_or(ctx, p, kernel);
         const bool aql = chain && nf == 1u &&
                          (kernel == rtk::kTraceSingle || kernel == rtk::kTraceSingleOne);
@@ -1940,6 +2199,29 @@ rt_status rt_band_costs(rt_ctx* ctx, uint32_t w, uint32_t h, const rt_band_set* 
         for (uint32_t x = 0; x < tiles_x; ++x) sum += c[(uint64_t)j * tiles_x + x];
         out_cost[j] = sum;
     }
+    return RT_OK;
+}
+
+rt_status rt_set_chain_parts(rt_ctx* ctx, uint32_t parts) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (parts > RT_MAX_CHAIN_PARTS)
+        return fail(RT_ERR_INVALID_ARGUMENT, "parts above RT_MAX_CHAIN_PARTS");
+    ctx->chain_parts = parts;
+    return RT_OK;
+}
+
+rt_status rt_chain_schedule(uint32_t frames, uint32_t cap, int variant, rt_chain_launch* out,
+                            uint32_t max_out, uint32_t* out_count) {
+    if (!out_count) return fail(RT_ERR_INVALID_ARGUMENT, "out_count is NULL");
+    if (frames == 0 || cap == 0) return fail(RT_ERR_INVALID_ARGUMENT, "frames or cap is 0");
+    if (variant < 0 || variant > kScheduleVariants)
+        return fail(RT_ERR_INVALID_ARGUMENT, "unknown schedule variant");
+    std::vector<rt_chain_launch> sched;
+    chain_schedule(frames, cap, variant, sched);
+    *out_count = (uint32_t)sched.size();
+    if (sched.size() > max_out || (!out && !sched.empty()))
+        return fail(RT_ERR_INVALID_SIZE, "the schedule has more launches than `out` holds");
+    std::copy(sched.begin(), sched.end(), out);
     return RT_OK;
 }
 

@@ -66,6 +66,8 @@ struct TraceParams {
     // update (rt_set_update_queues), each on its own stream: the wg_order list's sub-list
     // `part` (launch_wg_order with `parts`), or without an order every parts-th local band
     // from band `part`.  parts <= 1: the whole update.
+    // Fused frame-group launches (rt_set_chain_parts): tile_order is a unit order dealt into
+    // `parts` sub-lists and the launch runs sub-list `part` (rt_kernels.hip chain_part_grid).
     uint32_t part, parts;
     // Uniform XZ grid over the small spheres for bounce rays (rt_kernels.hip scan_grid;
     // built by rt_abi.cpp build_grid): per cell the range of its items, each item a copy
@@ -278,8 +280,15 @@ const char* trace_kernel_name();
 const char* single_kernel_name(uint32_t pix);
 // tile_order for launch_trace: the local tiles by decreasing recorded cost (quantised
 // log2 of tile_cost), so the slowest tiles start first and the cheap ones fill the tail.
+// dealt (non-null): a second copy of the order, dealt round-robin into dealt_parts contiguous
+// sub-lists (part_range) — the chain parts' table.
 hipError_t launch_tile_order(const uint32_t* tile_cost, uint32_t* tile_order, uint32_t tiles,
-                             uint32_t tiles_x, hipStream_t stream, uint32_t parts = 1);
+                             uint32_t tiles_x, hipStream_t stream, uint32_t parts = 1,
+                             uint32_t* dealt = nullptr, uint32_t dealt_parts = 1);
+// order[...] = the units (band << 16 | column) in raster order, dealt round-robin into `parts`
+// contiguous sub-lists (part_range)
+hipError_t launch_raster_order(uint32_t* order, uint32_t units, uint32_t units_x, uint32_t parts,
+                               hipStream_t stream);
 // The bounce split schedule's unit order (rt_kernels.hip rt_unit_order_kernel): a tile whose
 // recorded cost exceeds k_thr times the sum of all costs runs as `split` chunks of a
 // 1/split share each, and all units are ordered by their own cost, costliest first.

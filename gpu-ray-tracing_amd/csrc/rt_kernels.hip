@@ -2811,6 +2811,8 @@ rt_bounce_kernel(const TraceParams p) {
 // parts > 1: the sorted list is dealt round-robin into `parts` contiguous sub-lists (entry
 // pos to part pos % parts), one per concurrent part of a one-frame update (launch_single):
 // every part gets the same mix of costly and cheap workgroups, costliest first.
+// dealt (non-null): a second copy of the list dealt into dealt_parts sub-lists (the chain
+// parts of rt_update_frames, which run beside launches that use the undealt list).
 __device__ __forceinline__ uint32_t part_pos(uint32_t pos, uint32_t n, uint32_t parts) {
     if (parts <= 1u) return pos;
     const uint32_t k = pos % parts, j = pos / parts;
@@ -2819,7 +2821,9 @@ __device__ __forceinline__ uint32_t part_pos(uint32_t pos, uint32_t n, uint32_t 
 __global__ __launch_bounds__(1024) void rt_tile_order_kernel(const uint32_t* __restrict__ cost,
                                                              uint32_t* __restrict__ order,
                                                              uint32_t tiles, uint32_t tiles_x,
-                                                             uint32_t parts) {
+                                                             uint32_t parts,
+                                                             uint32_t* __restrict__ dealt,
+                                                             uint32_t dealt_parts) {
     constexpr uint32_t kBuckets = 128, kWaves = 16, kSlots = kBuckets * kWaves;
     __shared__ uint32_t hist[kSlots];          // [bucket][wave]
     __shared__ uint32_t scan[1024];
@@ -2876,18 +2880,36 @@ __global__ __launch_bounds__(1024) void rt_tile_order_kernel(const uint32_t* __r
             const uint32_t t = t0 + k * 1024u;
             if (t < tiles) {
                 const uint32_t pos = atomicAdd(&hist[bucket(c[k]) * kWaves + wave], 1u);
-                order[part_pos(pos, tiles, parts)] =
-                    ((t / tiles_x) << 16) | (t % tiles_x);
+                const uint32_t e = ((t / tiles_x) << 16) | (t % tiles_x);
+                order[part_pos(pos, tiles, parts)] = e;
+                if (dealt) dealt[part_pos(pos, tiles, dealt_parts)] = e;
             }
         }
     }
 }
 
 hipError_t launch_tile_order(const uint32_t* tile_cost, uint32_t* tile_order, uint32_t tiles,
-                             uint32_t tiles_x, hipStream_t stream, uint32_t parts) {
+                             uint32_t tiles_x, hipStream_t stream, uint32_t parts,
+                             uint32_t* dealt, uint32_t dealt_parts) {
     if (tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_tile_order_kernel, dim3(1), dim3(1024), 0, stream, tile_cost,
-                       tile_order, tiles, tiles_x, parts);
+                       tile_order, tiles, tiles_x, parts, dealt, dealt_parts);
+    return hipGetLastError();
+}
+
+// The units of a launch in raster order, dealt round-robin into `parts` sub-lists (the chain
+// parts of a generation whose costs are not measured yet).
+__global__ __launch_bounds__(256) void rt_raster_order_kernel(uint32_t* __restrict__ order,
+                                                              uint32_t units, uint32_t units_x,
+                                                              uint32_t parts) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t < units) order[part_pos(t, units, parts)] = ((t / units_x) << 16) | (t % units_x);
+}
+hipError_t launch_raster_order(uint32_t* order, uint32_t units, uint32_t units_x, uint32_t parts,
+                               hipStream_t stream) {
+    if (units == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_raster_order_kernel, dim3((units + 255u) / 256u), dim3(256), 0, stream,
+                       order, units, units_x, parts);
     return hipGetLastError();
 }
 
@@ -3424,11 +3446,30 @@ struct TraceArgs {
 };
 static_assert(offsetof(TraceArgs, p) == kParamsOff, "rt_trace_kernel's argument layout");
 
+// Chain parts (TraceParams::parts > 1 on a fused launch, rt_set_chain_parts): the launch runs
+// sub-list `part` of a unit order dealt into `parts` sub-lists (launch_tile_order's dealt copy
+// or launch_raster_order) as a one-row grid — workgroup i takes entry i of the sub-list, the
+// kernels' ordered path with the order pointer moved to the sub-list's first entry.  Only the
+// instances that read an order (`ordered`), and only with one; false otherwise.
+static bool chain_part_grid(const TraceParams& p, bool ordered, dim3& grid, uint32_t& first) {
+    first = 0;
+    if (p.parts <= 1u) return true;
+    if (!ordered || !p.tile_order || p.part >= p.parts) return false;
+    uint32_t len = 0;
+    part_range(grid.x * grid.y, p.parts, p.part, first, len);
+    grid = dim3(len, 1);
+    return true;
+}
+
 template <int kScan>
 static hipError_t launch_trace_as(const TraceParams& p, size_t lds, hipStream_t stream) {
     constexpr uint32_t w = wg_waves<kScan>();
-    const dim3 grid = tile_grid(p, is_group_kernel(kScan) ? 1u : w);
+    dim3 grid = tile_grid(p, is_group_kernel(kScan) ? 1u : w);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    uint32_t first = 0;
+    if (!chain_part_grid(p, kOrdered<kScan> && is_group_kernel(kScan), grid, first))
+        return hipErrorInvalidValue;
+    if (grid.x == 0) return hipSuccess;
     TraceArgs args;
     std::memset(&args, 0, offsetof(TraceArgs, p));
     args.cand = p.cand;
@@ -3438,6 +3479,7 @@ static hipError_t launch_trace_as(const TraceParams& p, size_t lds, hipStream_t 
     args.height = p.height;
     args.bands = pack_bands(p.band_first, p.band_step, p.tile_order != nullptr);
     args.p = p;
+    if (args.p.tile_order) args.p.tile_order += first;
     return launch_packed(kScan, reinterpret_cast<const void*>(&rt_trace_kernel<kScan>), grid,
                          dim3(64 * w), lds, stream, &args, sizeof(args));
 }
@@ -3446,9 +3488,12 @@ static hipError_t launch_trace_as(const TraceParams& p, size_t lds, hipStream_t 
 // (tile pairs, bands) — or the tile order's units in that shape.
 template <int G>
 static hipError_t launch_tpair(const TraceParams& p, hipStream_t stream) {
-    const dim3 grid((((p.width + 7u) >> 3) + 1u) >> 1, p.local_bands);
+    dim3 grid((((p.width + 7u) >> 3) + 1u) >> 1, p.local_bands);
     if (grid.x == 0 || grid.y == 0 || !p.cand) return grid.x && grid.y ? hipErrorInvalidValue
                                                                       : hipSuccess;
+    uint32_t first = 0;
+    if (!chain_part_grid(p, true, grid, first)) return hipErrorInvalidValue;
+    if (grid.x == 0) return hipSuccess;
     TraceArgs args;
     std::memset(&args, 0, offsetof(TraceArgs, p));
     args.cand = p.cand;
@@ -3458,6 +3503,7 @@ static hipError_t launch_tpair(const TraceParams& p, hipStream_t stream) {
     args.height = p.height;
     args.bands = pack_bands(p.band_first, p.band_step, p.tile_order != nullptr);
     args.p = p;
+    if (args.p.tile_order) args.p.tile_order += first;
     return launch_packed(G == 4 ? 9 : 10, reinterpret_cast<const void*>(&rt_tpair_kernel<G>),
                          grid, dim3(64 * G), 0, stream, &args, sizeof(args));
 }

@@ -147,6 +147,12 @@ _SIGS = {
     "rt_last_call_kernel_time": (ctypes.c_int, [P, ctypes.POINTER(F), ctypes.POINTER(U32)]),
 }
 
+# include/rt_chain_parts.h (the additions to rt_abi.h's boundary)
+_SIGS_CHAIN_PARTS = {
+    "rt_set_chain_parts": (ctypes.c_int, [P, U32]),
+    "rt_chain_schedule": (ctypes.c_int, [U32, U32, ctypes.c_int, P, U32, ctypes.POINTER(U32)]),
+}
+
 
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
@@ -165,7 +171,13 @@ class LaunchInfoC(ctypes.Structure):
     """rt_launch_info (rt_abi.h)."""
     _fields_ = [("launches", U32), ("frames", U32), ("max_frames_per_launch", U32),
                 ("kernel", ctypes.c_int32), ("queues", U32), ("submit", U32),
-                ("normal_rn", U32)]
+                ("normal_rn", U32), ("chain_parts", U32)]
+
+
+class ChainLaunchC(ctypes.Structure):
+    """rt_chain_launch (rt_abi.h): frames [first, first + frames) of a call for part `part`."""
+    _fields_ = [("part", U32), ("first", U32), ("frames", U32)]
+
 
 _lib = None
 
@@ -179,7 +191,7 @@ def lib() -> ctypes.CDLL:
             raise RuntimeError(f"librt_hip.so not found at {path}: build it with "
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -218,6 +230,10 @@ def fastcall():
 
 def exported_symbols() -> list[str]:
     return list(_SIGS)
+
+
+def chain_parts_symbols() -> list[str]:
+    return list(_SIGS_CHAIN_PARTS)
 
 
 def check(status: int, func: str) -> None:

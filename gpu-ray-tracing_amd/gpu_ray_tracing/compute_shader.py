@@ -73,6 +73,16 @@ def stripe_band_set(height: int, rank: int, nranks: int) -> tuple[int, int, int]
     return (rank, nranks, (bands - rank + nranks - 1) // nranks if bands > rank else 0)
 
 
+def chain_schedule(frames: int, cap: int, variant: int = 0) -> list[tuple[int, int, int]]:
+    """rt_chain_schedule: the (part, first frame, frames) launches of an update_frames call of
+    `frames` frames at `cap` frames per launch, in issue order (host only)."""
+    n = _lib.U32(0)
+    out = (_lib.ChainLaunchC * (2 * (int(frames) // max(1, int(cap)) + 4)))()
+    _lib.call("rt_chain_schedule", int(frames), int(cap), int(variant), out, len(out),
+              ctypes.byref(n))
+    return [(int(l.part), int(l.first), int(l.frames)) for l in out[:n.value]]
+
+
 def partition_bands(band_cost, nranks: int) -> list[tuple[int, int, int]]:
     """rt_partition_bands: the bands cut into nranks contiguous ranges (first, 1, count)
     whose largest cost is the smallest possible (host-only, exact)."""
@@ -130,6 +140,12 @@ class ComputeShaderPipeline:
         """rt_set_update_queues: one-frame updates of update_frames as `queues` concurrent
         parts on their own streams (0 = automatic, 1 = one launch per update)."""
         _lib.call("rt_set_update_queues", self._ctx, int(queues))
+
+    def set_chain_parts(self, parts: int) -> None:
+        """rt_set_chain_parts: update_frames calls of several fused frame-group launches as
+        two staggered chains over halves of the image (0 = automatic, 1 = one chain, 2 = two
+        parts wherever the conditions hold); identical pixels."""
+        _lib.call("rt_set_chain_parts", self._ctx, int(parts))
 
     def set_update_submit(self, mode: str) -> None:
         """rt_set_update_submit: how update_frames submits one-frame updates — "auto" (HIP

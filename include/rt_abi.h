@@ -206,8 +206,9 @@ RT_API const char* rt_kernel_name(int which);
 /* What the last rt_update / rt_render / rt_render_stripes / rt_update_frames call on this
  * context launched: trace launches, frames traced, the most frames one launch carried, the
  * instance of its last launch (RT_KERNEL_*, -1 before any launch), the concurrent parts
- * (streams or queues) its last frame ran as (rt_set_update_queues; each part is one launch)
- * and how its last launch was submitted (RT_SUBMIT_HIP or RT_SUBMIT_AQL). */
+ * (streams or queues) its last frame ran as (rt_set_update_queues; each part is one launch),
+ * how its last launch was submitted (RT_SUBMIT_HIP or RT_SUBMIT_AQL) and the chain parts its
+ * fused launches ran as (rt_set_chain_parts; `launches` counts every part's launches). */
 typedef struct rt_launch_info {
     uint32_t launches;
     uint32_t frames;
@@ -219,6 +220,9 @@ typedef struct rt_launch_info {
      * upload to give the IEEE quotient for every numerator and each of the scene's distinct
      * radii, at most 16 of them); 0: two correction steps */
     uint32_t normal_rn;
+    /* 2: the call's fused frame-group launches ran as two staggered chains (rt_set_chain_parts);
+     * 1 otherwise (appended: the fields above keep their offsets) */
+    uint32_t chain_parts;
 } rt_launch_info;
 RT_API rt_status rt_last_launch_info(const rt_ctx* ctx, rt_launch_info* out);
 /* Diagnostic: the per-tile candidate lists of camera rays the context built last (culled
@@ -322,7 +326,7 @@ RT_API rt_status rt_set_frame_images(rt_ctx* ctx, int mode);
  * per tile).  The groups' waves own one tile (ON: 2 waves, QUAD: 4) or a pair of adjacent
  * tiles, each lane tracing one pixel of each (ON2: 2 waves, QUAD2: 4; ABI 6).  AUTO
  * (default): 4 waves per tile for launches of at most 6144 tiles (small per-rank shares),
- * 4 waves per pair of tiles up to 12288 tiles, 2 waves per pair above (whole images) — the
+ * 4 waves per pair of tiles up to 20000 tiles, 2 waves per pair above (whole images) — the
  * pair forms when candidate lists exist, else 2 waves per tile; OFF: one wave per tile. */
 #define RT_FRAME_PAIRS_AUTO 0
 #define RT_FRAME_PAIRS_OFF 1
@@ -352,6 +356,8 @@ RT_API rt_status rt_set_tile_order(rt_ctx* ctx, int mode);
  * launch per update, at most RT_MAX_UPDATE_QUEUES.  Pixel results are identical. */
 #define RT_MAX_UPDATE_QUEUES 4u
 RT_API rt_status rt_set_update_queues(rt_ctx* ctx, uint32_t queues);
+/* Chain parts (rt_set_chain_parts, rt_chain_schedule: two staggered chains of fused launches
+ * per rt_update_frames call) are declared in rt_chain_parts.h. */
 /* How rt_update_frames submits one-frame updates when a call carries two or more of them.
  *   RT_SUBMIT_HIP   HIP launches on the caller's stream (and the context's extra streams for
  *                   concurrent parts).

@@ -1,7 +1,7 @@
 """Per-rank frame time of the stripe partition on ONE GPU (diagnostic, not the bench): times
 rank 0's share of a W x H progressive render for world sizes 1, 2, 4, 8, i.e. what each rank
 of `bench.py --gpus N` computes per step, to predict strong-scaling efficiency without an
-8-GPU node.  usage: [RT_FRAME_PAIRS=auto|off|on] [RT_TILE_ORDER=auto|off] [RT_FPL=n] [RT_IMAGES=last_two|every] [RT_QUEUES=q] [RT_SUBMIT=auto|hip|aql] [RT_REPS=r] [RT_WARM_MS=50] [RT_PATHS=auto|per_wave|pair|compact] python tools/rank_sim.py [K3|K2|K5] [steps]"""
+8-GPU node.  usage: [RT_FRAME_PAIRS=auto|off|on] [RT_TILE_ORDER=auto|off] [RT_FPL=n] [RT_IMAGES=last_two|every] [RT_QUEUES=q] [RT_CHAIN_PARTS=0|1|2] [RT_SUBMIT=auto|hip|aql] [RT_REPS=r] [RT_WARM_MS=50] [RT_PATHS=auto|per_wave|pair|compact] python tools/rank_sim.py [K3|K2|K5] [steps]"""
 import json
 import os
 import sys
@@ -40,6 +40,8 @@ def main(cfg="K3", steps=50):
         pipe.set_tile_order(os.environ.get("RT_TILE_ORDER", "auto"))
     if hasattr(rt._lib.lib(), "rt_set_update_queues"):
         pipe.set_update_queues(int(os.environ.get("RT_QUEUES", "0")))
+    if hasattr(rt._lib.lib(), "rt_set_chain_parts"):
+        pipe.set_chain_parts(int(os.environ.get("RT_CHAIN_PARTS", "0")))
     if hasattr(rt._lib.lib(), "rt_set_update_submit"):
         pipe.set_update_submit(os.environ.get("RT_SUBMIT", "auto"))
     # untimed warm-up (as bench.py --warm-ms): the whole image for RT_WARM_MS ms
@@ -78,6 +80,8 @@ def main(cfg="K3", steps=50):
                           "host_issue_us_per_step": round(host_us, 2),
                           "runs_us": [round(x, 2) for x in runs],
                           "queues": pipe.last_launch_info().get("queues"),
+                          "chain_parts": pipe.last_launch_info().get("chain_parts"),
+                          "launches": pipe.last_launch_info().get("launches"),
                           "kernel": pipe.last_launch_info().get("kernel_name"),
                           "frames_per_launch": pipe.last_launch_info().get("max_frames_per_launch"),
                           "submit": pipe.last_launch_info().get("submit")}), flush=True)
