@@ -19,6 +19,7 @@
 
 #include "rt_abi.h"
 #include "rt_chain_parts.h"
+#include "rt_selftest_roots.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -2363,6 +2364,33 @@ rt_status rt_selftest_fastmath(rt_ctx* ctx, uint64_t n_random, uint64_t out[5]) 
     (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, "rt_selftest_kernel");
     for (int i = 0; i < 5; ++i) out[i] = h[i];
+    return RT_OK;
+}
+
+rt_status rt_selftest_roots(rt_ctx* ctx, uint64_t n_random,
+                            rt_roots_tally out[RT_ROOTS_FAMILIES * RT_ROOTS_STRATA]) {
+    static_assert(RT_ROOTS_FAMILIES == rtk::kRootFamilies && RT_ROOTS_STRATA == rtk::kRootStrata,
+                  "rt_selftest_roots.h and rt_kernels.h disagree");
+    constexpr size_t kN = RT_ROOTS_FAMILIES * RT_ROOTS_STRATA * 4u;
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    unsigned long long* d = nullptr;
+    hipError_t e = hipMalloc(&d, kN * sizeof(unsigned long long));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(selftest roots)");
+    unsigned long long h[kN] = {};
+    e = hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rtk::launch_selftest_roots(d, n_random, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(e, "rt_selftest_roots_kernel");
+    for (size_t i = 0; i < kN / 4u; ++i) {
+        out[i].mismatches = h[4 * i];
+        out[i].drawn = h[4 * i + 1];
+        out[i].compared = h[4 * i + 2];
+        out[i].rooted = h[4 * i + 3];
+    }
     return RT_OK;
 }
 

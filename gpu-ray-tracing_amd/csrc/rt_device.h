@@ -179,7 +179,11 @@ RT_HD float reflectance(float cos_t, float ri) {
 // Used where the operands are in the domain by construction or by a wave-wide check
 // (rt_kernels.hip: defocus disk, roots, normal, sky, metal / dielectric normalisations);
 // tests/test_gpu_parity.py::test_fastmath_selftest checks both against the IEEE operations
-// on the GPU over that domain, and the root selection built on them against consider().
+// on the GPU over that domain; the root selections built on them (consider_fast,
+// consider_any_fast) are compared with consider() / consider_any() over the domain their
+// guards admit — origin components below 2^39, |C| + |R| <= 2^40, |d|^2 in [2^-11, 2^20],
+// any radius — by rt_selftest_roots (tests/test_fast_domains.py), which also reports how
+// many of its cases were inside that domain and really compared.
 __device__ __forceinline__ float rcp_refined(float b) {
     const float r = __builtin_amdgcn_rcpf(b);
     return fmaf(fmaf(-b, r, 1.0f), r, r);

@@ -297,6 +297,10 @@ hipError_t launch_unit_order(const uint32_t* tile_cost, uint32_t* unit_order,
                              uint32_t split, float k_thr, hipStream_t stream);
 // Exact fast-path self-test (rt_selftest_fastmath): cnt[5] device counters, zeroed.
 hipError_t launch_selftest(unsigned long long* cnt, uint64_t n_rand, hipStream_t stream);
+// Root-selection self-test (rt_selftest_roots): cnt[kRootFamilies * kRootStrata * 4] device
+// counters, zeroed; per family and stratum mismatches, drawn, compared, rooted.
+constexpr uint32_t kRootFamilies = 2, kRootStrata = 4;
+hipError_t launch_selftest_roots(unsigned long long* cnt, uint64_t n_rand, hipStream_t stream);
 // bad[0] |= 1 unless div_rn(a, R, rcp_refined(R)) == a / R for every numerator significand
 // (binades 2^0 and 2^-100) and each of the n distinct radii (device array)
 hipError_t launch_rcp_check(const float* radii, uint32_t n, uint32_t* bad, hipStream_t stream);

@@ -153,6 +153,13 @@ _SIGS_CHAIN_PARTS = {
     "rt_chain_schedule": (ctypes.c_int, [U32, U32, ctypes.c_int, P, U32, ctypes.POINTER(U32)]),
 }
 
+# include/rt_selftest_roots.h
+_SIGS_SELFTEST_ROOTS = {
+    "rt_selftest_roots": (ctypes.c_int, [P, ctypes.c_uint64, P]),
+}
+RT_ROOTS_FAMILIES = 2
+RT_ROOTS_STRATA = 4
+
 
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
@@ -179,6 +186,12 @@ class ChainLaunchC(ctypes.Structure):
     _fields_ = [("part", U32), ("first", U32), ("frames", U32)]
 
 
+class RootsTallyC(ctypes.Structure):
+    """rt_roots_tally (rt_selftest_roots.h): one family and stratum of rt_selftest_roots."""
+    _fields_ = [("mismatches", ctypes.c_uint64), ("drawn", ctypes.c_uint64),
+                ("compared", ctypes.c_uint64), ("rooted", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -191,7 +204,7 @@ def lib() -> ctypes.CDLL:
             raise RuntimeError(f"librt_hip.so not found at {path}: build it with "
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
-        for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS}.items():
+        for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -234,6 +247,10 @@ def exported_symbols() -> list[str]:
 
 def chain_parts_symbols() -> list[str]:
     return list(_SIGS_CHAIN_PARTS)
+
+
+def selftest_roots_symbols() -> list[str]:
+    return list(_SIGS_SELFTEST_ROOTS)
 
 
 def check(status: int, func: str) -> None:

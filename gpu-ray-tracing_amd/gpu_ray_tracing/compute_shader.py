@@ -232,6 +232,19 @@ class ComputeShaderPipeline:
         _lib.call("rt_selftest_fastmath", self._ctx, n_random, out)
         return list(out)
 
+    ROOT_FAMILIES = ("consider_fast", "consider_any_fast")
+    ROOT_STRATA = ("bulk", "far", "edge", "far_edge")
+
+    def selftest_roots(self, n_random: int = 1 << 26) -> dict:
+        """rt_selftest_roots: {(family, stratum): {mismatches, drawn, compared, rooted}} of
+        the fast root selections against the IEEE ones on n_random generated cases."""
+        out = (_lib.RootsTallyC * (_lib.RT_ROOTS_FAMILIES * _lib.RT_ROOTS_STRATA))()
+        _lib.call("rt_selftest_roots", self._ctx, n_random, out)
+        return {(fam, st): {k: int(getattr(out[f * _lib.RT_ROOTS_STRATA + s], k))
+                            for k, _ in _lib.RootsTallyC._fields_}
+                for f, fam in enumerate(self.ROOT_FAMILIES)
+                for s, st in enumerate(self.ROOT_STRATA)}
+
     def __del__(self):
         try:
             self.close()

@@ -1107,9 +1107,12 @@ def test_image_files_from_device(rt, pipe, tmp_path):
 
 def test_fastmath_selftest(rt):
     """The exact fast paths of division / sqrt (rt_device.h) return the IEEE bits: all 2^32
-    inputs of the defocus-disk normalisation, 2^26 random division and sqrt cases, and
-    the scan's root selection on them (consider_fast) picks the same root and sphere as
-    the IEEE one on 2^26 random camera-domain rays and spheres."""
+    inputs of the defocus-disk normalisation (out[0]) and of sqrt_core above 2^-96 (out[2]),
+    2^26 random division and accumulator cases (out[1]), and on 2^26 generated rays and
+    spheres of the guards' domain the root selections built on them (consider_fast and
+    consider_any_fast) pick the same root and sphere as the IEEE ones (out[3]: the cases in
+    which either differs; test_fast_domains.py::test_root_selection_selftest checks, through
+    rt_selftest_roots, how many of those cases were really compared)."""
     p = rt.ComputeShaderPipeline(0)
     out = p.selftest_fastmath(1 << 26)
     p.close()
