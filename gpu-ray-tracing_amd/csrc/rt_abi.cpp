@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_aov.h"
 #include "rt_chain_parts.h"
 #include "rt_selftest_roots.h"
 #include "rt_device.h"
@@ -148,6 +149,8 @@ struct rt_ctx {
     hipEvent_t time_ev[2] = {};
     bool timing = false;
     uint32_t timed_launches = 0;
+    // rt_pick's record on the device: four 16-B slots (id, hit, normal, material)
+    float4* d_pick = nullptr;
 };
 
 namespace {
@@ -1368,6 +1371,47 @@ rt_status trace(rt_ctx* ctx, const float* in, float* out, uint32_t w, uint32_t h
     return RT_OK;
 }
 
+// Shared body of rt_trace_aov / rt_trace_aov_bands / rt_pick (rt_aov.h): argument checks and
+// scene upload as prepare(), then one rt_aov_kernel launch over the band set — or, for a pick
+// (pick_lane != 0), over the one tile (tx0, bs.first).  Of the context's state it touches the
+// sphere records alone: no candidate lists, orders, counts, launch info or timing events.
+rt_status trace_aov(rt_ctx* ctx, const rt_aov_planes* planes, uint32_t w, uint32_t h,
+                    const rt_band_set& bs, const rt_scene_camera* cam, const rt_sphere* spheres,
+                    uint32_t count, hipStream_t stream, uint32_t tx0, uint32_t pick_lane) {
+    if (!planes || !cam) return fail(RT_ERR_INVALID_ARGUMENT, "NULL planes or camera");
+    if (!planes->sphere_id && !planes->hit && !planes->normal && !planes->material)
+        return fail(RT_ERR_INVALID_ARGUMENT, "no plane requested");
+    if (rt_status s = check_image(w, h)) return s;
+    if (rt_status s = check_band_set(h, bs)) return s;
+    if (rt_status s = upload_spheres(ctx, spheres, count, stream)) return s;
+    if (bs.count == 0) return RT_OK;
+    rtk::AovParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.id = planes->sphere_id;
+    p.hit = reinterpret_cast<float4*>(planes->hit);
+    p.normal = reinterpret_cast<float4*>(planes->normal);
+    p.material = reinterpret_cast<float4*>(planes->material);
+    p.geom = ctx->d_geom;
+    p.sph = ctx->d_sph;
+    p.width = w;
+    p.height = h;
+    p.count = count;
+    p.bands = rtk::pack_bands(bs.first, bs.step, false);
+    p.tx0 = tx0;
+    p.culled = ctx->scan_mode == RT_SCAN_CULLED ? 1u : 0u;
+    p.pick = pick_lane;
+    for (int i = 0; i < 3; ++i) {
+        p.center[i] = cam->center[i];
+        p.vul[i] = cam->viewport_upper_left[i];
+        p.pdu[i] = cam->pixel_delta_u[i];
+        p.pdv[i] = cam->pixel_delta_v[i];
+    }
+    const uint32_t tiles_x = pick_lane ? 1u : (w + 7u) >> 3;
+    hipError_t e = rtk::launch_aov(p, tiles_x, bs.count, stream);
+    if (e != hipSuccess) return hip_fail(e, "rt_aov_kernel launch");
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1459,6 +1503,7 @@ rt_status rt_destroy(rt_ctx* ctx) {
         (void)hipFree(ctx->split_col);
         (void)hipFree(ctx->split_cnt);
         (void)hipFree(ctx->unit_order);
+        (void)hipFree(ctx->d_pick);
         free_candidates(ctx);
         for (uint32_t k = 0; k + 1 < RT_MAX_UPDATE_QUEUES; ++k) {
             if (ctx->aux[k]) (void)hipStreamDestroy(ctx->aux[k]);
@@ -1622,6 +1667,64 @@ rt_status rt_render(rt_ctx* ctx, const float* in, float* out, uint32_t w, uint32
                     const rt_scene_camera* cam, const rt_sphere* spheres, uint32_t count,
                     uint32_t frames, const float* seeds, void* stream) {
     return trace(ctx, in, out, w, h, 0, 1, cam, spheres, count, frames, seeds, stream);
+}
+
+rt_status rt_trace_aov_bands(rt_ctx* ctx, const rt_aov_planes* planes, uint32_t w, uint32_t h,
+                             const rt_band_set* bands, const rt_scene_camera* cam,
+                             const rt_sphere* spheres, uint32_t count, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!bands) return fail(RT_ERR_INVALID_ARGUMENT, "bands is NULL");
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    return trace_aov(ctx, planes, w, h, *bands, cam, spheres, count,
+                     static_cast<hipStream_t>(stream), 0u, 0u);
+}
+
+rt_status rt_trace_aov(rt_ctx* ctx, const rt_aov_planes* planes, uint32_t w, uint32_t h,
+                       const rt_scene_camera* cam, const rt_sphere* spheres, uint32_t count,
+                       void* stream) {
+    const rt_band_set all = stripe_set(h, 0, 1);
+    return rt_trace_aov_bands(ctx, planes, w, h, &all, cam, spheres, count, stream);
+}
+
+rt_status rt_pick(rt_ctx* ctx, uint32_t w, uint32_t h, uint32_t x, uint32_t y,
+                  const rt_scene_camera* cam, const rt_sphere* spheres, uint32_t count,
+                  void* stream_v, rt_pick_result* out) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (rt_status s = check_image(w, h)) return s;
+    if (x >= w || y >= h) return fail(RT_ERR_INVALID_ARGUMENT, "pixel outside the image");
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (!ctx->d_pick) {
+        hipError_t e = hipMalloc(&ctx->d_pick, 4 * sizeof(float4));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(pick record)");
+    }
+    // the one wave of the pixel's tile; its record lands in element 0 of each "plane"
+    rt_aov_planes planes;
+    planes.sphere_id = reinterpret_cast<uint32_t*>(ctx->d_pick);
+    planes.hit = reinterpret_cast<float*>(ctx->d_pick + 1);
+    planes.normal = reinterpret_cast<float*>(ctx->d_pick + 2);
+    planes.material = reinterpret_cast<float*>(ctx->d_pick + 3);
+    const rt_band_set band = {y / RT_STRIPE_ROWS, 1u, 1u};
+    const uint32_t lane = (y % RT_STRIPE_ROWS) * 8u + (x & 7u);
+    if (rt_status s = trace_aov(ctx, &planes, w, h, band, cam, spheres, count, stream, x >> 3,
+                                lane + 1u))
+        return s;
+    float rec[16];
+    hipError_t e = hipMemcpyAsync(rec, ctx->d_pick, sizeof(rec), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "rt_pick read-back");
+    std::memcpy(&out->sphere_id, &rec[0], sizeof(uint32_t));
+    out->t = rec[7];
+    for (int i = 0; i < 3; ++i) {
+        out->p[i] = rec[4 + i];
+        out->normal[i] = rec[8 + i];
+    }
+    out->front_face = rec[11] != 0.0f ? 1u : 0u;
+    for (int i = 0; i < 4; ++i) out->color[i] = rec[12 + i];
+    return RT_OK;
 }
 
 }  // extern "C"

@@ -275,6 +275,26 @@ hipError_t launch_deinterleave(const float4* gathered, float4* out, uint32_t wid
 // for the linear encoding.
 hipError_t launch_present(const float4* in, uchar4* out, uint64_t texels,
                           const float* srgb_t, hipStream_t stream);
+// First-hit G-buffer (rt_aov.h; rt_kernels.hip rt_aov_kernel): the hit record of each pixel's
+// centre ray, written out instead of shaded.  Planes not wanted are null (not all of them).
+struct AovParams {
+    uint32_t* id;        // per pixel: the winning sphere's index, RT_AOV_MISS for none
+    float4* hit;         // (p, t)
+    float4* normal;      // (n, front ? 1 : 0)
+    float4* material;    // the sphere's color[4]
+    const float4* geom;  // the context's scan records and sphere records (TraceParams)
+    const float4* sph;
+    uint32_t width, height, count;
+    uint32_t bands;      // pack_bands(first, step, false): the planes' stripe map
+    uint32_t tx0;        // tile column of the launch's first wave
+    uint32_t culled;     // 1: per-wave cone culling (RT_SCAN_CULLED), 0: the exhaustive walk
+    // rt_pick: lane + 1 of the one pixel wanted, whose record goes to element 0 of each plane
+    // (0: every live lane stores at its pixel)
+    uint32_t pick;
+    float center[3], vul[3], pdu[3], pdv[3];
+};
+// waves tx0 .. tx0 + tiles_x - 1 of local bands [0, bands): one wave per 8x8 tile
+hipError_t launch_aov(const AovParams& p, uint32_t tiles_x, uint32_t bands, hipStream_t stream);
 const char* trace_kernel_name();
 // "rt_single_kernel<p>": p = pix tiles per wave (0: kTraceSingle's)
 const char* single_kernel_name(uint32_t pix);

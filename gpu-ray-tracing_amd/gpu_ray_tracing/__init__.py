@@ -16,11 +16,15 @@ from .scene import (SCENE_DEFAULT, SCENE_N, SCENE_THREE, SphereCollection,
                     create_default_spheres, frame_seeds, synthetic_scene, three_spheres)
 
 RtError = _lib.RtError
+# first-hit G-buffer (include/rt_aov.h): the plane names of ComputeShaderPipeline.trace_aov
+# and the sphere_id of a miss (-1 as the plane's int32)
+AOV_PLANES = _lib.AOV_PLANES
+RT_AOV_MISS = _lib.RT_AOV_MISS
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
     "ComputeShaderNode", "SphereCollection", "create_default_spheres", "synthetic_scene",
     "three_spheres", "frame_seeds", "stripe_local_rows", "RT_STRIPE_ROWS", "RtError",
     "SCENE_THREE", "SCENE_DEFAULT", "SCENE_N", "srgb_thresholds", "image_io",
-    "partition_bands", "chain_schedule", "stripe_band_set",
+    "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
 ]

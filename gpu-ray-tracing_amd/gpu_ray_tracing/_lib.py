@@ -160,6 +160,26 @@ _SIGS_SELFTEST_ROOTS = {
 RT_ROOTS_FAMILIES = 2
 RT_ROOTS_STRATA = 4
 
+# include/rt_aov.h (first-hit G-buffer and picking)
+_SIGS_AOV = {
+    "rt_trace_aov": (ctypes.c_int, [P, P, U32, U32, P, P, U32, P]),
+    "rt_trace_aov_bands": (ctypes.c_int, [P, P, U32, U32, P, P, P, U32, P]),
+    "rt_pick": (ctypes.c_int, [P, U32, U32, U32, U32, P, P, U32, P, P]),
+}
+RT_AOV_MISS = 0xFFFFFFFF
+AOV_PLANES = ("sphere_id", "hit", "normal", "material")
+
+
+class AovPlanesC(ctypes.Structure):
+    """rt_aov_planes (rt_aov.h): device pointers, NULL = plane not wanted."""
+    _fields_ = [("sphere_id", P), ("hit", P), ("normal", P), ("material", P)]
+
+
+class PickResultC(ctypes.Structure):
+    """rt_pick_result (rt_aov.h)."""
+    _fields_ = [("sphere_id", U32), ("t", F), ("p", F * 3), ("normal", F * 3),
+                ("front_face", U32), ("color", F * 4)]
+
 
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
@@ -204,7 +224,8 @@ def lib() -> ctypes.CDLL:
             raise RuntimeError(f"librt_hip.so not found at {path}: build it with "
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
-        for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS}.items():
+        for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
+                                  **_SIGS_AOV}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -251,6 +272,10 @@ def chain_parts_symbols() -> list[str]:
 
 def selftest_roots_symbols() -> list[str]:
     return list(_SIGS_SELFTEST_ROOTS)
+
+
+def aov_symbols() -> list[str]:
+    return list(_SIGS_AOV)
 
 
 def check(status: int, func: str) -> None:

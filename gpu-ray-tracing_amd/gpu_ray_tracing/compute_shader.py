@@ -452,6 +452,65 @@ class ComputeShaderPipeline:
         _lib.call("rt_deinterleave_stripes", self._ctx, _ptr(gathered), _ptr(out), width,
                   height, nranks, self._stream())
 
+    # ---- first-hit G-buffer and picking (rt_aov.h) -------------------------------------
+    def trace_aov(self, width: int, height: int, camera: SceneCamera,
+                  spheres: SphereCollection, planes=_lib.AOV_PLANES, bands=None,
+                  out: dict | None = None) -> dict[str, torch.Tensor]:
+        """rt_trace_aov / rt_trace_aov_bands: the first hit of each pixel's centre ray from
+        camera.center (no jitter, no lens), bit-identical to the oracle's sphere_hit.
+        planes: any non-empty subset of "sphere_id" ((rows, W) int32, a miss reads -1: the
+        bits of RT_AOV_MISS), "hit" ((rows, W, 4) float32: p, t; a miss 0, 0, 0, +inf),
+        "normal" (n, front ? 1 : 0; a miss zeros) and "material" (the sphere's color[4]; a
+        miss zeros).  bands = (first, step, count): compact local buffers of count * 8 rows
+        with global pixel coordinates, as update_frames_bands.  Buffers come from `out` (by
+        plane name) where given, else they are allocated on the pipeline's device; a buffer
+        of a plane not in `planes` is not touched.  Enqueued on torch's current stream."""
+        planes = tuple(planes)
+        unknown = [k for k in planes if k not in _lib.AOV_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {_lib.AOV_PLANES}")
+        rows = height if bands is None else int(bands[2]) * RT_STRIPE_ROWS
+        res: dict[str, torch.Tensor] = {}
+        c = _lib.AovPlanesC()
+        for name in planes:
+            is_id = name == "sphere_id"
+            dtype = torch.int32 if is_id else torch.float32
+            t = out.get(name) if out else None
+            if t is None:
+                shape = (rows, width) if is_id else (rows, width, 4)
+                t = torch.empty(shape, dtype=dtype, device=self.torch_device)
+            need = rows * width * (1 if is_id else 4)
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < need):
+                raise ValueError(f"out[{name!r}] must be a contiguous CUDA (HIP) {dtype} tensor "
+                                 f"of at least {need} elements")
+            setattr(c, name, t.data_ptr())
+            res[name] = t
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        if bands is None:
+            _lib.call("rt_trace_aov", self._ctx, ctypes.byref(c), width, height,
+                      ctypes.byref(cam), p, n, self._stream())
+        else:
+            _lib.call("rt_trace_aov_bands", self._ctx, ctypes.byref(c), width, height,
+                      _lib.band_sets([bands]), ctypes.byref(cam), p, n, self._stream())
+        return res
+
+    def pick(self, width: int, height: int, x: int, y: int, camera: SceneCamera,
+             spheres: SphereCollection) -> dict | None:
+        """rt_pick: what is under pixel (x, y) — {"sphere_id", "t", "p", "normal",
+        "front_face", "color"}, the texel trace_aov writes there — or None for a miss.  One
+        wave is launched (the pixel's tile); returns once the record is on the host."""
+        r = _lib.PickResultC()
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        _lib.call("rt_pick", self._ctx, width, height, x, y, ctypes.byref(cam), p, n,
+                  self._stream(), ctypes.byref(r))
+        if r.sphere_id == _lib.RT_AOV_MISS:
+            return None
+        return {"sphere_id": int(r.sphere_id), "t": np.float32(r.t),
+                "p": np.array(r.p, np.float32), "normal": np.array(r.normal, np.float32),
+                "front_face": bool(r.front_face), "color": np.array(r.color, np.float32)}
 
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:

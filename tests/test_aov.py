@@ -1,0 +1,569 @@
+"""First-hit G-buffer and picking (include/rt_aov.h): rt_trace_aov, rt_trace_aov_bands, rt_pick.
+
+Every plane is compared bit for bit (NaN == NaN) with a reference built in this file from the
+oracle's exported sphere_hit (oracle_sphere_hit, wgsl:182-221): the ray through the pixel's
+centre from camera.center — pc = fma(y + .5, pdv, fma(x + .5, pdu, vul)) with libm's fmaf, the
+operand order of the oracle's get_ray with both offsets 0 — walked over the spheres in index
+order with tmin = 0.001 and a running tmax from 3.4e35 (sphere_list_hit, wgsl:164-180).
+
+The CPU tests check the boundary (exports, the header as C11 and C++17) and, from the reference
+alone, that every case reaches the edge it names; they print the counts (run with -s).  A miss
+pixel and a hit pixel are asked of every case that can have both: the 1 x 1 image has one pixel
+(a hit), inside the glass sphere every pixel hits and with no sphere every pixel misses by
+construction, and the degenerate camera's result is whatever the reference says.
+"""
+import ctypes
+import ctypes.util
+import functools
+import re
+import subprocess
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from conftest import bits_equal
+
+gpu = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = ROOT / "include" / "rt_aov.h"
+LIB = ROOT / "gpu-ray-tracing_amd" / "build" / "librt_hip.so"
+F32 = np.float32
+W, H = 37, 21                 # two partial tile columns (37 = 4 * 8 + 5), a partial tile row
+PLANES = ("sphere_id", "hit", "normal", "material")
+FLOAT_PLANES = PLANES[1:]
+MISS = -1                     # RT_AOV_MISS as the id plane's int32
+CULL_MIN = 32                 # rt_kernels.hip kCullMinSpheres: the cone route starts here
+RT_ERR_INVALID_ARGUMENT = 1
+SENT_F, SENT_I = -12345.0, 0x5A5A5A5A
+TAIL = 16                     # 64 bytes of sentinel after every plane
+
+
+# ---- the reference ----------------------------------------------------------------------------
+@functools.lru_cache(None)
+def _fmaf():
+    m = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    m.fmaf.restype = ctypes.c_float
+    m.fmaf.argtypes = [ctypes.c_float] * 3
+    return m.fmaf
+
+
+def centre_ray(blob, x, y):
+    """(o, d) of global pixel (x, y): six f32 each."""
+    fmaf = _fmaf()
+    b = np.asarray(blob, F32)
+    o, vul, pdu, pdv = b[0:3], b[4:7], b[8:11], b[12:15]
+    sx, sy = F32(x) + F32(0.5), F32(y) + F32(0.5)
+    ray = np.empty(6, F32)
+    ray[0:3] = o
+    for k in range(3):
+        pc = F32(fmaf(sy, pdv[k], fmaf(sx, pdu[k], vul[k])))
+        ray[3 + k] = pc - o[k]
+    return ray
+
+
+def reference(blob, spheres, w, h):
+    """The four planes of a w x h image (read-only arrays)."""
+    from oracle import oracle
+    hit_fn = oracle.lib().oracle_sphere_hit
+    sph = np.ascontiguousarray(spheres, F32).reshape(-1, 8)
+    base = sph.ctypes.data
+    recs = [ctypes.c_void_p(base + 32 * i) for i in range(sph.shape[0])]
+    ray = np.zeros(6, F32)
+    out = np.zeros(8, F32)
+    pray, pout = ctypes.c_void_p(ray.ctypes.data), ctypes.c_void_p(out.ctypes.data)
+    tmin = ctypes.c_float(0.001)
+    ids = np.full((h, w), MISS, np.int32)
+    hit = np.zeros((h, w, 4), F32)
+    hit[..., 3] = np.inf
+    normal = np.zeros((h, w, 4), F32)
+    material = np.zeros((h, w, 4), F32)
+    with np.errstate(all="ignore"):
+        for y in range(h):
+            for x in range(w):
+                ray[:] = centre_ray(blob, x, y)
+                tmax = ctypes.c_float(3.4e35)
+                for i, rec in enumerate(recs):
+                    if hit_fn(rec, pray, tmin, tmax, pout):
+                        tmax = ctypes.c_float(out[0])
+                        ids[y, x] = i
+                        hit[y, x, :3], hit[y, x, 3] = out[1:4], out[0]
+                        normal[y, x] = out[4:8]
+                        material[y, x] = sph[i, 4:8]
+    res = {"sphere_id": ids, "hit": hit, "normal": normal, "material": material}
+    for a in res.values():
+        a.setflags(write=False)
+    return res
+
+
+# ---- cases --------------------------------------------------------------------------------------
+def default_camera(rt, w, h, **settings):
+    return rt.SceneCamera.from_settings(rt.CameraSettings(**settings), w, h, 0.5)
+
+
+def glass_index(spheres):
+    """The large glass sphere (radius 1 at (0, 1, 0), material code > 1)."""
+    s = np.asarray(spheres)
+    (idx,) = np.nonzero((s[:, 3] == 1.0) & (s[:, 7] > 1.0) & (s[:, 0] == 0.0))
+    return int(idx[0])
+
+
+def _three(rt):
+    return rt.three_spheres().spheres
+
+
+def _n40(rt):
+    return rt.synthetic_scene(40).spheres
+
+
+CASES = {
+    # scenes under the default camera: the exhaustive route (3 < 32) and the cone route
+    "three": lambda rt: (W, H, default_camera(rt, W, H), _three(rt)),
+    "n40": lambda rt: (W, H, default_camera(rt, W, H), _n40(rt)),
+    "default": lambda rt: (W, H, default_camera(rt, W, H), rt.create_default_spheres(1).spheres),
+    # exactly one tile, one live lane, partial tiles both ways, one band
+    "8x8": lambda rt: (8, 8, default_camera(rt, 8, 8), _three(rt)),
+    "1x1": lambda rt: (1, 1, default_camera(rt, 1, 1), _three(rt)),
+    "9x17": lambda rt: (9, 17, default_camera(rt, 9, 17), _three(rt)),
+    "64x8": lambda rt: (64, 8, default_camera(rt, 64, 8), _three(rt)),
+    # look_from inside the large glass sphere, looking at the metal one: second roots
+    "inside": lambda rt: (W, H, default_camera(rt, W, H, look_from=(0.25, 1.0, 0.5),
+                                               look_at=(4.0, 1.0, 0.0), field_of_view=60.0),
+                          _n40(rt)),
+    # the last two records are the same bytes
+    "tie": lambda rt: (W, H, default_camera(rt, W, H),
+                       np.concatenate([_n40(rt), _n40(rt)[-1:]])),
+    "tie3": lambda rt: (W, H, default_camera(rt, W, H),
+                        np.concatenate([_three(rt), _three(rt)[-1:]])),
+    "zero": lambda rt: (W, H, default_camera(rt, W, H), np.zeros((0, 8), F32)),
+    "one": lambda rt: (W, H, default_camera(rt, W, H), _three(rt)[0:1]),
+    "defocus0": lambda rt: (W, H, default_camera(rt, W, H, defocus_angle=0.0), _n40(rt)),
+    "bands": lambda rt: (W, 40, default_camera(rt, W, 40), _n40(rt)),
+    "undisturbed_aov": lambda rt: (64, 40, default_camera(rt, 64, 40, look_from=(3.0, 1.5, 13.0)),
+                                   _n40(rt)),
+    "stream_b": lambda rt: (W, H, default_camera(rt, W, H), rt.synthetic_scene(48, seed=7).spheres),
+}
+
+
+def _degenerate(rt, scene):
+    cam = default_camera(rt, W, H)
+    cam = cam.with_fields(viewport_upper_left=cam.center, pixel_delta_u=(0.0, 0.0, 0.0),
+                          pixel_delta_v=(0.0, 0.0, 0.0))
+    return W, H, cam, scene(rt)
+
+
+CASES["degenerate"] = lambda rt: _degenerate(rt, _three)
+CASES["degenerate40"] = lambda rt: _degenerate(rt, _n40)
+
+SMALL = ["three", "8x8", "1x1", "9x17", "64x8", "tie3", "one", "degenerate"]
+CONE = ["n40", "default", "inside", "tie", "defocus0", "bands", "undisturbed_aov", "stream_b",
+        "degenerate40"]
+BOTH_KINDS = [n for n in CASES if n not in ("1x1", "inside", "zero", "degenerate", "degenerate40")]
+
+
+@functools.lru_cache(None)
+def case(name):
+    """A case's camera, scene and reference planes, computed once and shared (read-only)."""
+    import gpu_ray_tracing as rt
+    w, h, cam, spheres = CASES[name](rt)
+    spheres = np.ascontiguousarray(spheres, F32).reshape(-1, 8)
+    spheres.setflags(write=False)
+    return SimpleNamespace(name=name, w=w, h=h, cam=cam, spheres=spheres,
+                           sc=rt.SphereCollection(spheres),
+                           want=reference(cam.blob, spheres, w, h))
+
+
+# ---- CPU tests ------------------------------------------------------------------------------------
+def test_library_exports_the_aov_entry_points(rt):
+    want = {"rt_trace_aov", "rt_trace_aov_bands", "rt_pick"}
+    assert set(rt._lib.aov_symbols()) == want
+    nm = subprocess.run(["nm", "-D", "--defined-only", str(LIB)], capture_output=True,
+                        text=True, check=True).stdout
+    assert want <= set(re.findall(r" T (rt_\w+)$", nm, flags=re.M))
+    declared = set(re.findall(r"RT_API\s+rt_status\s+(rt_\w+)\s*\(", HEADER.read_text()))
+    assert declared == want
+    assert rt._lib.lib().rt_abi_version() == 7
+    assert rt.RT_AOV_MISS == 0xFFFFFFFF and np.uint32(rt.RT_AOV_MISS).view(np.int32) == MISS
+    assert ctypes.sizeof(rt._lib.AovPlanesC) == 32 and ctypes.sizeof(rt._lib.PickResultC) == 52
+
+
+@pytest.mark.parametrize("lang,std,cc", [("c", "c11", "gcc"), ("c++", "c++17", "g++")])
+def test_header_compiles_on_its_own(lang, std, cc):
+    r = subprocess.run([cc, f"-std={std}", "-Wall", "-Werror", "-fsyntax-only", "-x", lang,
+                        "-I", str(HEADER.parent), "-include", "rt_aov.h", "/dev/null"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def _counts(c):
+    ids = c.want["sphere_id"]
+    return int((ids == MISS).sum()), int((ids != MISS).sum())
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_cases_reach_their_edges(name):
+    c = case(name)
+    miss, hits = _counts(c)
+    n = c.spheres.shape[0]
+    ids, nrm, t = c.want["sphere_id"], c.want["normal"], c.want["hit"][..., 3]
+    back = int(((ids != MISS) & (nrm[..., 3] == 0.0)).sum())
+    print(f"{name}: {c.w}x{c.h}, {n} spheres, {miss} miss, {hits} hit, {back} back-face, "
+          f"{len(np.unique(ids[ids != MISS]))} distinct winners, {int(np.isnan(t).sum())} NaN t")
+    assert miss + hits == c.w * c.h
+    if name in BOTH_KINDS:
+        assert miss >= 1 and hits >= 1
+    if name in SMALL:
+        assert n < CULL_MIN
+    if name in CONE:
+        assert n >= CULL_MIN
+    if name == "1x1":
+        assert hits == 1
+    if name == "zero":
+        assert n == 0 and hits == 0
+    if name == "one":
+        assert n == 1
+    if name == "inside":
+        g = glass_index(c.spheres)
+        assert miss == 0 and back >= 1
+        assert (ids == g).all() and back == c.w * c.h     # every pixel leaves the glass sphere
+    if name in ("tie", "tie3"):
+        assert c.spheres[-1].tobytes() == c.spheres[-2].tobytes()
+        lower = int((ids == n - 2).sum())
+        print(f"{name}: {lower} pixels won by the lower twin, {int((ids == n - 1).sum())} by the upper")
+        assert lower >= 1 and not (ids == n - 1).any()
+    if name.startswith("degenerate"):
+        rays = np.array([centre_ray(c.cam.blob, x, y)[3:] for y in (0, c.h - 1)
+                         for x in (0, c.w - 1)])
+        assert (rays == 0.0).all()
+
+
+def test_defocus_fields_differ_but_rays_do_not():
+    a, b = case("n40"), case("defocus0")
+    assert a.cam.defocus_angle > 0.0 and b.cam.defocus_angle == 0.0
+    assert a.cam.blob.tobytes() != b.cam.blob.tobytes()
+    for k in PLANES:
+        assert a.want[k].tobytes() == b.want[k].tobytes()
+
+
+def test_pick_pixels_cover_hit_and_miss():
+    c = case("n40")
+    ids = c.want["sphere_id"]
+    kinds = {bool(ids[y, x] != MISS) for x, y in pick_pixels(c)}
+    assert kinds == {True, False}
+
+
+# ---- GPU side ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def pipe(rt):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    p = rt.ComputeShaderPipeline(0)
+    yield p
+    p.close()
+
+
+def guarded(p, rows, w, planes=PLANES):
+    """Plane buffers of rows x w pixels followed by a 64-byte tail of sentinel."""
+    import torch
+    out = {}
+    for k in planes:
+        n = rows * w * (1 if k == "sphere_id" else 4)
+        if k == "sphere_id":
+            out[k] = torch.full((n + TAIL,), SENT_I, dtype=torch.int32, device=p.torch_device)
+        else:
+            out[k] = torch.full((n + TAIL,), SENT_F, dtype=torch.float32, device=p.torch_device)
+    return out
+
+
+def to_host(res, rows, w):
+    """{plane: (image part, tail part)} as numpy arrays, after a synchronise."""
+    import torch
+    torch.cuda.synchronize()
+    got = {}
+    for k, t in res.items():
+        a = t.cpu().numpy().reshape(-1)
+        n = rows * w * (1 if k == "sphere_id" else 4)
+        got[k] = (a[:n].reshape((rows, w) if k == "sphere_id" else (rows, w, 4)), a[n:])
+    return got
+
+
+def trace(p, c, planes=PLANES, bands=None, rows=None):
+    """The planes of case c (numpy) from guarded buffers; asserts the tails are untouched."""
+    rows = c.h if rows is None else rows
+    out = guarded(p, rows, c.w, planes)
+    res = p.trace_aov(c.w, c.h, c.cam, c.sc, planes=planes, bands=bands, out=out)
+    assert set(res) == set(planes)
+    got = to_host(res, rows, c.w)
+    for k, (_, tail) in got.items():
+        assert tail.size == TAIL and (tail == (SENT_I if k == "sphere_id" else F32(SENT_F))).all(), \
+            f"{k}: the 64 bytes after the plane were written"
+    return {k: v[0] for k, v in got.items()}
+
+
+def differences(got, want, what=""):
+    wrong = []
+    for k in got:
+        if k == "sphere_id":
+            bad = int((got[k] != want[k]).sum())
+        else:
+            bad = bits_equal(got[k], want[k])[1]
+        if bad:
+            wrong.append(f"{what}{k}: {bad} values differ")
+    return wrong
+
+
+MODES = ["culled", "exhaustive"]
+
+
+@gpu
+@pytest.mark.parametrize("name", ["three", "n40", "default"])
+def test_scenes_match_reference_in_both_scan_modes(pipe, name):
+    c = case(name)
+    got = {}
+    for mode in MODES:
+        pipe.set_scan_mode(mode)
+        got[mode] = trace(pipe, c)
+        assert not differences(got[mode], c.want, f"{mode} ")
+    assert not differences(got["culled"], got["exhaustive"], "culled vs exhaustive ")
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", ["8x8", "1x1", "9x17", "64x8"])
+def test_partial_tiles_and_buffer_end(pipe, name, mode):
+    pipe.set_scan_mode(mode)
+    c = case(name)
+    assert not differences(trace(pipe, c), c.want)
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_plane_subsets(pipe, mode):
+    import torch
+    pipe.set_scan_mode(mode)
+    c = case("n40")
+    full = trace(pipe, c)
+    assert not differences(full, c.want)
+    for planes in [(k,) for k in PLANES] + [("sphere_id", "normal")]:
+        # every plane's buffer goes in through `out`; only the requested ones may change
+        out = guarded(pipe, c.h, c.w)
+        res = pipe.trace_aov(c.w, c.h, c.cam, c.sc, planes=planes, out=out)
+        assert set(res) == set(planes)
+        got = to_host(out, c.h, c.w)
+        for k in PLANES:
+            sent = SENT_I if k == "sphere_id" else F32(SENT_F)
+            assert (got[k][1] == sent).all(), f"{planes}: tail of {k} written"
+            if k in planes:
+                assert not differences({k: got[k][0]}, full, f"{planes} ")
+            else:
+                assert (got[k][0] == sent).all(), f"{planes}: unrequested plane {k} written"
+    torch.cuda.synchronize()
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", ["inside", "tie", "tie3", "zero", "one", "degenerate",
+                                  "degenerate40"])
+def test_edge_scenes_match_reference(pipe, name, mode):
+    pipe.set_scan_mode(mode)
+    c = case(name)
+    got = trace(pipe, c)
+    assert not differences(got, c.want)
+    n = c.spheres.shape[0]
+    if name == "inside":
+        assert (got["normal"][..., 3] == 0.0).all() and (got["sphere_id"] != MISS).all()
+    if name in ("tie", "tie3"):
+        assert not (got["sphere_id"] == n - 1).any() and (got["sphere_id"] == n - 2).any()
+    if name == "zero":
+        assert (got["sphere_id"] == MISS).all()
+        assert (got["hit"][..., :3] == 0.0).all() and np.isposinf(got["hit"][..., 3]).all()
+        assert not got["normal"].any() and not got["material"].any()
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_defocus_is_ignored(pipe, mode):
+    pipe.set_scan_mode(mode)
+    a, b = case("n40"), case("defocus0")
+    ga, gb = trace(pipe, a), trace(pipe, b)
+    assert not differences(ga, gb, "defocus 0.6 vs 0 ")
+    assert not differences(ga, a.want)
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_bands_equal_the_whole_image_rows(rt, pipe, mode):
+    pipe.set_scan_mode(mode)
+    c = case("bands")
+    whole = trace(pipe, c)
+    assert not differences(whole, c.want)
+    sets = [rt.stripe_band_set(c.h, r, 3) for r in range(3)] + [(1, 1, 3)]
+    assert sets[:3] == [(0, 3, 2), (1, 3, 2), (2, 3, 1)]
+    for first, step, count in sets:
+        got = trace(pipe, c, bands=(first, step, count), rows=8 * count)
+        for j in range(count):
+            g0 = 8 * (first + j * step)
+            local = {k: v[8 * j:8 * j + 8] for k, v in got.items()}
+            rows = {k: v[g0:g0 + 8] for k, v in whole.items()}
+            assert not differences(local, rows, f"band set {(first, step, count)} local band {j} ")
+    # an empty set: RT_OK and nothing written
+    out = guarded(pipe, 8, c.w)
+    pipe.trace_aov(c.w, c.h, c.cam, c.sc, bands=(0, 1, 0), out=out)
+    for k, (img, tail) in to_host(out, 8, c.w).items():
+        sent = SENT_I if k == "sphere_id" else F32(SENT_F)
+        assert (img == sent).all() and (tail == sent).all(), f"empty band set wrote {k}"
+
+
+def pick_pixels(c):
+    ids = c.want["sphere_id"]
+    ys, xs = np.nonzero(ids == MISS)
+    interior = [(int(x), int(y)) for x, y in zip(xs, ys) if 0 < x < c.w - 1 and 0 < y < c.h - 1]
+    return [(0, 0), (c.w - 1, 0), (0, c.h - 1), (c.w - 1, c.h - 1), (c.w // 2, c.h // 2),
+            interior[0]]
+
+
+@gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_pick_equals_the_planes_texel(rt, pipe, mode):
+    pipe.set_scan_mode(mode)
+    c = case("n40")
+    planes = trace(pipe, c)
+    assert not differences(planes, c.want)
+    for x, y in pick_pixels(c):
+        r = pipe.pick(c.w, c.h, x, y, c.cam, c.sc)
+        sid = int(planes["sphere_id"][y, x])
+        if sid == MISS:
+            assert r is None, (x, y)
+            continue
+        assert r is not None and r["sphere_id"] == sid, (x, y)
+        assert bits_equal(r["p"], planes["hit"][y, x, :3])[0], (x, y)
+        assert bits_equal(r["t"], planes["hit"][y, x, 3])[0], (x, y)
+        assert bits_equal(r["normal"], planes["normal"][y, x, :3])[0], (x, y)
+        assert r["front_face"] == bool(planes["normal"][y, x, 3]), (x, y)
+        assert bits_equal(r["color"], planes["material"][y, x])[0], (x, y)
+    # a miss through the C struct itself: id RT_AOV_MISS, t = +inf, zeros elsewhere
+    x, y = pick_pixels(c)[-1]
+    rec = rt._lib.PickResultC()
+    cam = c.cam.to_c()
+    p, n = pipe._spheres(c.sc)
+    rt._lib.call("rt_pick", pipe._ctx, c.w, c.h, x, y, ctypes.byref(cam), p, n, pipe._stream(),
+                 ctypes.byref(rec))
+    assert rec.sphere_id == rt.RT_AOV_MISS and np.isposinf(rec.t) and rec.front_face == 0
+    assert not any(rec.p) and not any(rec.normal) and not any(rec.color)
+    for x, y in [(c.w, 0), (0, c.h)]:
+        with pytest.raises(rt.RtError) as e:
+            pipe.pick(c.w, c.h, x, y, c.cam, c.sc)
+        assert e.value.status == RT_ERR_INVALID_ARGUMENT
+
+
+@gpu
+@pytest.mark.parametrize("depth", [1, 3])
+def test_render_is_undisturbed(rt, oracle, depth):
+    """4 frames of update_frames, against 2 frames + trace_aov from another camera + pick + 2
+    frames on the same context: the same two images, the oracle's, and no trace of the
+    G-buffer calls in the launch info or the candidate lists."""
+    import torch
+    w, h = 64, 40
+    g = case("undisturbed_aov")
+    scene = rt.SphereCollection(g.spheres)
+    cam = rt.SceneCamera.from_settings(rt.CameraSettings(max_depth=depth), w, h, 0.5)
+    still = cam.with_fields(camera_has_moved=0.0)
+    seeds = np.array(rt.frame_seeds(5, 4), F32)
+    want, cur = [], np.zeros((h, w, 4), F32)
+    for k, s in enumerate(seeds):
+        cur, _ = oracle.update(cur, (cam if k == 0 else still).with_fields(
+            random_seed=float(s)).blob, g.spheres)
+        want.append(cur)
+    p = rt.ComputeShaderPipeline(0)
+    try:
+        a, b = p.new_image(w, h), p.new_image(w, h)
+        p.update_frames(a, b, w, h, cam, scene, seeds)
+        torch.cuda.synchronize()
+        seq_a = (a.cpu().numpy(), b.cpu().numpy())
+        a2, b2 = p.new_image(w, h), p.new_image(w, h)
+        p.update_frames(a2, b2, w, h, cam, scene, seeds[:2])
+        info, stats = p.last_launch_info(), p.candidate_stats()
+        planes = p.trace_aov(w, h, g.cam, scene)
+        picked = p.pick(w, h, 40, 30, g.cam, scene)
+        assert p.last_launch_info() == info
+        assert p.candidate_stats() == stats
+        p.update_frames(a2, b2, w, h, still, scene, seeds[2:])
+        torch.cuda.synchronize()
+        seq_b = (a2.cpu().numpy(), b2.cpu().numpy())
+        got = {k: v.cpu().numpy() for k, v in planes.items()}
+    finally:
+        p.close()
+    assert not differences(got, g.want, "the G-buffer in between ")
+    sid = int(g.want["sphere_id"][30, 40])
+    assert (picked is None) == (sid == MISS) and (picked is None or picked["sphere_id"] == sid)
+    for i, name in enumerate("ab"):
+        assert bits_equal(seq_b[i], seq_a[i])[0], f"image_{name} differs between the sequences"
+    # frame f writes image_b for even f: image_a holds frame 3, image_b frame 2
+    assert bits_equal(seq_a[0], want[3])[0] and bits_equal(seq_a[1], want[2])[0]
+    assert bits_equal(seq_b[0], want[3])[0] and bits_equal(seq_b[1], want[2])[0]
+
+
+@gpu
+def test_stream_order_after_set_spheres(rt):
+    import torch
+    a, b = case("n40"), case("stream_b")
+    p = rt.ComputeShaderPipeline(0)
+    try:
+        first = p.trace_aov(a.w, a.h, a.cam, a.sc)
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            p.set_spheres(b.sc)
+            res = p.trace_aov(b.w, b.h, b.cam, b.sc)
+        side.synchronize()
+        got = {k: v.cpu().numpy() for k, v in res.items()}
+        got_a = {k: v.cpu().numpy() for k, v in first.items()}
+    finally:
+        p.close()
+    assert not differences(got_a, a.want, "first scene ")
+    assert not differences(got, b.want, "new scene on the side stream ")
+
+
+@gpu
+def test_errors_launch_nothing(rt, pipe):
+    c = case("three")
+    L = rt._lib
+    out = guarded(pipe, c.h, c.w)
+    planes = L.AovPlanesC(*[out[k].data_ptr() for k in PLANES])
+    cam = c.cam.to_c()
+    sp, n = pipe._spheres(c.sc)
+    stream = pipe._stream()
+    bands = L.band_sets([(0, 1, 1)])
+    calls = {
+        "all planes NULL": lambda: L.call("rt_trace_aov", pipe._ctx, ctypes.byref(L.AovPlanesC()),
+                                          c.w, c.h, ctypes.byref(cam), sp, n, stream),
+        "all planes NULL (bands)": lambda: L.call("rt_trace_aov_bands", pipe._ctx,
+                                                  ctypes.byref(L.AovPlanesC()), c.w, c.h, bands,
+                                                  ctypes.byref(cam), sp, n, stream),
+        "planes NULL": lambda: L.call("rt_trace_aov", pipe._ctx, None, c.w, c.h,
+                                      ctypes.byref(cam), sp, n, stream),
+        "camera NULL": lambda: L.call("rt_trace_aov", pipe._ctx, ctypes.byref(planes), c.w, c.h,
+                                      None, sp, n, stream),
+        "spheres NULL": lambda: L.call("rt_trace_aov", pipe._ctx, ctypes.byref(planes), c.w, c.h,
+                                       ctypes.byref(cam), None, 3, stream),
+        "bands NULL": lambda: L.call("rt_trace_aov_bands", pipe._ctx, ctypes.byref(planes), c.w,
+                                     c.h, None, ctypes.byref(cam), sp, n, stream),
+        "pick camera NULL": lambda: L.call("rt_pick", pipe._ctx, c.w, c.h, 0, 0, None, sp, n,
+                                           stream, ctypes.byref(L.PickResultC())),
+        "pick out NULL": lambda: L.call("rt_pick", pipe._ctx, c.w, c.h, 0, 0, ctypes.byref(cam),
+                                        sp, n, stream, None),
+    }
+    for what, fn in calls.items():
+        with pytest.raises(rt.RtError) as e:
+            fn()
+        assert e.value.status == RT_ERR_INVALID_ARGUMENT, what
+    with pytest.raises(rt.RtError) as e:
+        pipe.trace_aov(c.w, c.h, c.cam, c.sc, planes=())
+    assert e.value.status == RT_ERR_INVALID_ARGUMENT
+    for k, (img, tail) in to_host(out, c.h, c.w).items():
+        sent = SENT_I if k == "sphere_id" else F32(SENT_F)
+        assert (img == sent).all() and (tail == sent).all(), f"a refused call wrote {k}"
+    # the context still works
+    assert not differences(trace(pipe, c), c.want)
