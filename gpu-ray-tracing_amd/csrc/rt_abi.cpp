@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +21,9 @@
 #include "rt_abi.h"
 #include "rt_aov.h"
 #include "rt_chain_parts.h"
+#include "rt_denoise.h"
 #include "rt_selftest_roots.h"
+#include "rt_denoise_kernels.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -1724,6 +1727,69 @@ rt_status rt_pick(rt_ctx* ctx, uint32_t w, uint32_t h, uint32_t x, uint32_t y,
     }
     out->front_face = rec[11] != 0.0f ? 1u : 0u;
     for (int i = 0; i < 4; ++i) out->color[i] = rec[12 + i];
+    return RT_OK;
+}
+
+void rt_denoise_params_default(rt_denoise_params* p) {
+    if (!p) return;
+    p->iterations = 5u;
+    p->normal_power_log2 = 5u;
+    p->inv_sigma_color2 = 1.0f;
+    p->inv_sigma_position2 = 4.0f;
+}
+
+// One launch per iteration (rt_denoise.hip).  The last iteration writes dst, so iteration i
+// writes dst when the number of iterations after it is even and scratch when it is odd; src is
+// read by iteration 0 alone.  Steps up to 16 stage their texels in LDS, larger steps load every
+// tap from global memory; RT_DENOISE_ROUTE=direct (environment, diagnostic)
+// takes that route at every step.  Of the context only the device is used.
+rt_status rt_denoise(rt_ctx* ctx, const float* src, float* dst, float* scratch, uint32_t w,
+                     uint32_t h, const float* hit, const float* normal, const uint32_t* sphere_id,
+                     const rt_denoise_params* params, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!src || !dst || !hit || !normal || !params)
+        return fail(RT_ERR_INVALID_ARGUMENT, "NULL src, dst, hit, normal or params");
+    if (dst == src) return fail(RT_ERR_INVALID_ARGUMENT, "dst is src");
+    const uint32_t n = params->iterations;
+    if (n < 1u || n > RT_DENOISE_MAX_ITERATIONS)
+        return fail(RT_ERR_INVALID_ARGUMENT, "iterations outside 1..RT_DENOISE_MAX_ITERATIONS");
+    if (params->normal_power_log2 > 10u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "normal_power_log2 above 10");
+    const float ic0 = params->inv_sigma_color2, ip = params->inv_sigma_position2;
+    if (!(ic0 >= 0.0f) || !(ip >= 0.0f) || std::isinf(ic0) || std::isinf(ip))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a sigma term is negative, NaN or infinite");
+    if (n >= 2u && (!scratch || scratch == src || scratch == dst))
+        return fail(RT_ERR_INVALID_ARGUMENT, "iterations >= 2 need a scratch image of their own");
+    if (rt_status s = check_image(w, h)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    const char* env = std::getenv("RT_DENOISE_ROUTE");
+    const bool direct = env && !std::strcmp(env, "direct");
+    rtk::DenoiseParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.hit = reinterpret_cast<const float4*>(hit);
+    p.normal = reinterpret_cast<const float4*>(normal);
+    p.id = sphere_id;
+    p.width = w;
+    p.height = h;
+    p.npow = params->normal_power_log2;
+    p.ip = ip;
+    const float4* in = reinterpret_cast<const float4*>(src);
+    float ic = ic0;                                       // ic0 * 4^i: exact, or +inf
+    for (uint32_t i = 0; i < n; ++i) {
+        float4* out = reinterpret_cast<float4*>((n - 1u - i) % 2u == 0u ? dst : scratch);
+        p.in = in;
+        p.out = out;
+        p.shift = i;
+        p.ic = std::min(ic, FLT_MAX);
+        const rtk::DenoiseRoute route = !direct && (1u << i) <= rtk::kDenoiseRowsMaxStep
+                                            ? rtk::kDenoiseRows
+                                            : rtk::kDenoiseDirect;
+        hipError_t e = rtk::launch_denoise(p, route, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return hip_fail(e, "rt_denoise_kernel launch");
+        in = out;
+        ic = ic * 4.0f;
+    }
     return RT_OK;
 }
 

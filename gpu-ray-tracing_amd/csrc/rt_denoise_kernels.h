@@ -1,0 +1,34 @@
+// rt_denoise_kernels.h — launch interface of the denoiser's kernels (rt_denoise.hip) for
+// rt_abi.cpp.  Internal; the public boundary is include/rt_denoise.h.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace rtk {
+
+// How one iteration reaches its 25 taps (rt_denoise.hip).
+enum DenoiseRoute : uint32_t {
+    kDenoiseRows = 0,    // LDS: 64 x 4 pixels of one (y mod step) class of rows with a halo of
+                         // 2 * step along x (step <= kDenoiseRowsMaxStep)
+    kDenoiseDirect = 1,  // no LDS: every tap is a global load, one wave per 64-pixel row piece
+};
+
+struct DenoiseParams {
+    const float4* in;      // this iteration's input image
+    float4* out;
+    const float4* hit;     // guide planes of rt_trace_aov
+    const float4* normal;
+    const uint32_t* id;    // null: no id test
+    uint32_t width, height;
+    uint32_t shift;        // log2 of the tap spacing
+    uint32_t npow;         // the normal weight is squared this many times
+    float ic, ip;          // this iteration's 1 / sigma_c^2 (clamped to FLT_MAX), 1 / sigma_p^2
+};
+
+// kDenoiseRows with a step above this is hipErrorInvalidValue.
+constexpr uint32_t kDenoiseRowsMaxStep = 16;
+hipError_t launch_denoise(const DenoiseParams& p, DenoiseRoute route, hipStream_t stream);
+
+}  // namespace rtk

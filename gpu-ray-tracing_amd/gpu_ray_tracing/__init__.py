@@ -8,7 +8,7 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (RT_STRIPE_ROWS, ComputeShaderImages, ComputeShaderNode,
+from .compute_shader import (DENOISE_DEFAULTS, RT_STRIPE_ROWS, ComputeShaderImages, ComputeShaderNode,
                              ComputeShaderPipeline, chain_schedule, partition_bands,
                              srgb_thresholds,
                              stripe_band_set, stripe_local_rows)
@@ -20,6 +20,8 @@ RtError = _lib.RtError
 # and the sphere_id of a miss (-1 as the plane's int32)
 AOV_PLANES = _lib.AOV_PLANES
 RT_AOV_MISS = _lib.RT_AOV_MISS
+# the denoiser (include/rt_denoise.h): ComputeShaderPipeline.denoise's default parameters
+RT_DENOISE_MAX_ITERATIONS = _lib.RT_DENOISE_MAX_ITERATIONS
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
@@ -27,4 +29,5 @@ __all__ = [
     "three_spheres", "frame_seeds", "stripe_local_rows", "RT_STRIPE_ROWS", "RtError",
     "SCENE_THREE", "SCENE_DEFAULT", "SCENE_N", "srgb_thresholds", "image_io",
     "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
+    "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS",
 ]

@@ -181,6 +181,20 @@ class PickResultC(ctypes.Structure):
                 ("front_face", U32), ("color", F * 4)]
 
 
+# include/rt_denoise.h (the a-trous denoiser guided by rt_aov.h's planes)
+_SIGS_DENOISE = {
+    "rt_denoise_params_default": (None, [P]),
+    "rt_denoise": (ctypes.c_int, [P, P, P, P, U32, U32, P, P, P, P, P]),
+}
+RT_DENOISE_MAX_ITERATIONS = 8
+
+
+class DenoiseParamsC(ctypes.Structure):
+    """rt_denoise_params (rt_denoise.h), 16 bytes."""
+    _fields_ = [("iterations", U32), ("normal_power_log2", U32), ("inv_sigma_color2", F),
+                ("inv_sigma_position2", F)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -225,7 +239,7 @@ def lib() -> ctypes.CDLL:
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
-                                  **_SIGS_AOV}.items():
+                                  **_SIGS_AOV, **_SIGS_DENOISE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -276,6 +290,10 @@ def selftest_roots_symbols() -> list[str]:
 
 def aov_symbols() -> list[str]:
     return list(_SIGS_AOV)
+
+
+def denoise_symbols() -> list[str]:
+    return list(_SIGS_DENOISE)
 
 
 def check(status: int, func: str) -> None:

@@ -24,6 +24,17 @@ from .camera import SceneCamera
 from .scene import SphereCollection
 
 RT_STRIPE_ROWS = _lib.RT_STRIPE_ROWS
+# ComputeShaderPipeline.denoise's defaults: rt_denoise_params_default's (1 / 0.5^2 = 4)
+DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_color": 1.0,
+                    "sigma_position": 0.5}
+
+
+def inv_sigma2(sigma: float) -> float:
+    """1 / sigma^2 in float32, as denoise passes a sigma to rt_denoise (inf for sigma 0,
+    which the library refuses; 0 for an infinite sigma: that weight term is off)."""
+    with np.errstate(divide="ignore", over="ignore"):
+        s = np.float32(sigma)
+        return float(np.float32(1.0) / (s * s))
 
 
 def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
@@ -511,6 +522,58 @@ class ComputeShaderPipeline:
         return {"sphere_id": int(r.sphere_id), "t": np.float32(r.t),
                 "p": np.array(r.p, np.float32), "normal": np.array(r.normal, np.float32),
                 "front_face": bool(r.front_face), "color": np.array(r.color, np.float32)}
+
+    # ---- the denoiser (rt_denoise.h) -----------------------------------------------------
+    def denoise(self, image: torch.Tensor, width: int, height: int, guides: dict, *,
+                iterations: int = DENOISE_DEFAULTS["iterations"],
+                normal_power_log2: int = DENOISE_DEFAULTS["normal_power_log2"],
+                sigma_color: float = DENOISE_DEFAULTS["sigma_color"],
+                sigma_position: float = DENOISE_DEFAULTS["sigma_position"],
+                use_ids: bool = True, out: torch.Tensor | None = None,
+                scratch: torch.Tensor | None = None) -> torch.Tensor:
+        """rt_denoise: the edge-avoiding a-trous filter of rt_denoise.h over `image` (an
+        accumulator of width x height, left as it is), guided by the planes trace_aov returns
+        for the same view: guides["hit"], guides["normal"] and, with use_ids,
+        guides["sphere_id"].  Iteration i filters with tap spacing 1 << i; the sigmas go to the
+        library as float32 1 / sigma^2 (sigma_color is iteration 0's and halves every
+        iteration).  `out` and `scratch` (needed from two iterations on) are allocated when
+        not given; returns `out`, whose alpha is the image's.  Every bit equals the NumPy
+        restatement in tests/test_denoise.py.  Enqueued on torch's current stream."""
+        need = width * height * 4
+
+        def image_like(t, what, dtype=torch.float32, n=need):
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) {dtype} tensor of at "
+                                 f"least {n} elements")
+            return t
+
+        image_like(image, "image")
+        names = ("hit", "normal") + (("sphere_id",) if use_ids else ())
+        missing = [k for k in names if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"guides lacks {missing} (the planes of trace_aov)")
+        image_like(guides["hit"], 'guides["hit"]')
+        image_like(guides["normal"], 'guides["normal"]')
+        ids = None
+        if use_ids:
+            ids = image_like(guides["sphere_id"], 'guides["sphere_id"]', torch.int32,
+                             width * height)
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=self.torch_device)
+        image_like(out, "out")
+        if scratch is None and iterations >= 2:
+            scratch = torch.empty((height, width, 4), dtype=torch.float32,
+                                  device=self.torch_device)
+        if scratch is not None:
+            image_like(scratch, "scratch")
+        params = _lib.DenoiseParamsC(int(iterations), int(normal_power_log2),
+                                     inv_sigma2(sigma_color), inv_sigma2(sigma_position))
+        _lib.call("rt_denoise", self._ctx, _ptr(image), _ptr(out),
+                  _ptr(scratch) if scratch is not None else None, width, height,
+                  _ptr(guides["hit"]), _ptr(guides["normal"]),
+                  _ptr(ids) if ids is not None else None, ctypes.byref(params), self._stream())
+        return out
 
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:
