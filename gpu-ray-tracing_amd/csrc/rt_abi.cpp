@@ -22,8 +22,10 @@
 #include "rt_aov.h"
 #include "rt_chain_parts.h"
 #include "rt_denoise.h"
+#include "rt_reproject.h"
 #include "rt_selftest_roots.h"
 #include "rt_denoise_kernels.h"
+#include "rt_reproject_kernels.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -1790,6 +1792,102 @@ rt_status rt_denoise(rt_ctx* ctx, const float* src, float* dst, float* scratch, 
         in = out;
         ic = ic * 4.0f;
     }
+    return RT_OK;
+}
+
+void rt_reproject_params_default(rt_reproject_params* p) {
+    if (!p) return;
+    p->max_history = 64u;
+    p->lambertian_only = 1u;
+    p->position_tolerance2 = 1e-5f;
+    p->_reserved = 0u;
+}
+
+// The rows of the inverse of [du' dv' e'] in double, each operation as rt_reproject.h states it
+// (this file is built with -ffp-contract=off).
+rt_status rt_reproject_basis(const rt_scene_camera* cam, float out[9]) {
+    if (!cam || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL prev_camera or out");
+    double o[3], du[3], dv[3], e[3];
+    for (int k = 0; k < 3; ++k) {
+        o[k] = (double)cam->center[k];
+        du[k] = (double)cam->pixel_delta_u[k];
+        dv[k] = (double)cam->pixel_delta_v[k];
+        e[k] = (double)cam->viewport_upper_left[k] - o[k];
+    }
+    auto cross = [](const double* a, const double* b, double* r) {
+        r[0] = a[1] * b[2] - a[2] * b[1];
+        r[1] = a[2] * b[0] - a[0] * b[2];
+        r[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double c[3][3];
+    cross(dv, e, c[0]);
+    cross(e, du, c[1]);
+    cross(du, dv, c[2]);
+    const double det = (du[0] * c[0][0] + du[1] * c[0][1]) + du[2] * c[0][2];
+    if (det == 0.0 || !std::isfinite(det))
+        return fail(RT_ERR_INVALID_ARGUMENT, "degenerate prev_camera: [du dv e] is singular");
+    float rows[9];
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) {
+            rows[3 * i + k] = (float)(c[i][k] / det);
+            if (!std::isfinite(rows[3 * i + k]))
+                return fail(RT_ERR_INVALID_ARGUMENT,
+                            "degenerate prev_camera: the basis is not finite");
+        }
+    std::memcpy(out, rows, sizeof(rows));
+    return RT_OK;
+}
+
+// One launch (rt_reproject.hip).  Of the context the device is used, and dst's uniform-count
+// record is dropped: dst holds per-pixel counts afterwards.
+rt_status rt_reproject(rt_ctx* ctx, const float* prev, float* dst, uint32_t w, uint32_t h,
+                       const rt_scene_camera* prev_camera, const rt_reproject_planes* planes,
+                       const rt_reproject_params* params, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!prev || !dst || !prev_camera || !planes || !params)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "NULL prev_rgba, dst_rgba, prev_camera, planes or params");
+    if (dst == prev) return fail(RT_ERR_INVALID_ARGUMENT, "dst_rgba is prev_rgba");
+    if (params->max_history < 1u || params->max_history > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "max_history outside 1..16777216");
+    if (params->lambertian_only > 1u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "lambertian_only is neither 0 nor 1");
+    if (params->_reserved != 0u) return fail(RT_ERR_INVALID_ARGUMENT, "_reserved is not 0");
+    const float tol2 = params->position_tolerance2;
+    if (!(tol2 >= 0.0f) || std::isinf(tol2))
+        return fail(RT_ERR_INVALID_ARGUMENT, "position_tolerance2 is negative, NaN or infinite");
+    if (!planes->prev_sphere_id || !planes->prev_hit || !planes->sphere_id || !planes->hit ||
+        !planes->normal || (params->lambertian_only && !planes->material))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a required plane is NULL");
+    if (rt_status s = check_image(w, h)) return s;
+    rtk::ReprojectParams p;
+    std::memset(&p, 0, sizeof(p));
+    float rows[9];
+    if (rt_status s = rt_reproject_basis(prev_camera, rows)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    p.prev = reinterpret_cast<const float4*>(prev);
+    p.dst = reinterpret_cast<float4*>(dst);
+    p.prev_id = planes->prev_sphere_id;
+    p.prev_hit = reinterpret_cast<const float4*>(planes->prev_hit);
+    p.id = planes->sphere_id;
+    p.hit = reinterpret_cast<const float4*>(planes->hit);
+    p.normal = reinterpret_cast<const float4*>(planes->normal);
+    p.material = params->lambertian_only
+                     ? reinterpret_cast<const float4*>(planes->material) : nullptr;
+    p.width = w;
+    p.height = h;
+    for (int k = 0; k < 3; ++k) {
+        p.r0[k] = rows[k];
+        p.r1[k] = rows[3 + k];
+        p.r2[k] = rows[6 + k];
+        p.o[k] = prev_camera->center[k];
+    }
+    p.tol2 = tol2;
+    p.max_history = (float)params->max_history;
+    forget_count(ctx, dst);
+    hipError_t e = rtk::launch_reproject(p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "rt_reproject_kernel launch");
     return RT_OK;
 }
 

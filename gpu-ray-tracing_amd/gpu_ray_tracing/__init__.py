@@ -8,9 +8,10 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (DENOISE_DEFAULTS, RT_STRIPE_ROWS, ComputeShaderImages, ComputeShaderNode,
+from .compute_shader import (DENOISE_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
+                             ComputeShaderImages, ComputeShaderNode,
                              ComputeShaderPipeline, chain_schedule, partition_bands,
-                             srgb_thresholds,
+                             reproject_basis, srgb_thresholds,
                              stripe_band_set, stripe_local_rows)
 from .scene import (SCENE_DEFAULT, SCENE_N, SCENE_THREE, SphereCollection,
                     create_default_spheres, frame_seeds, synthetic_scene, three_spheres)
@@ -29,5 +30,5 @@ __all__ = [
     "three_spheres", "frame_seeds", "stripe_local_rows", "RT_STRIPE_ROWS", "RtError",
     "SCENE_THREE", "SCENE_DEFAULT", "SCENE_N", "srgb_thresholds", "image_io",
     "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
-    "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS",
+    "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
 ]

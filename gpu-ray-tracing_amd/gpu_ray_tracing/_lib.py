@@ -195,6 +195,26 @@ class DenoiseParamsC(ctypes.Structure):
                 ("inv_sigma_position2", F)]
 
 
+# include/rt_reproject.h (carrying the accumulator across camera moves)
+_SIGS_REPROJECT = {
+    "rt_reproject_params_default": (None, [P]),
+    "rt_reproject_basis": (ctypes.c_int, [P, P]),
+    "rt_reproject": (ctypes.c_int, [P, P, P, U32, U32, P, P, P, P]),
+}
+
+
+class ReprojectParamsC(ctypes.Structure):
+    """rt_reproject_params (rt_reproject.h), 16 bytes."""
+    _fields_ = [("max_history", U32), ("lambertian_only", U32), ("position_tolerance2", F),
+                ("_reserved", U32)]
+
+
+class ReprojectPlanesC(ctypes.Structure):
+    """rt_reproject_planes (rt_reproject.h): device pointers, 48 bytes."""
+    _fields_ = [("prev_sphere_id", P), ("prev_hit", P), ("sphere_id", P), ("hit", P),
+                ("normal", P), ("material", P)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -239,7 +259,7 @@ def lib() -> ctypes.CDLL:
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
-                                  **_SIGS_AOV, **_SIGS_DENOISE}.items():
+                                  **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -294,6 +314,10 @@ def aov_symbols() -> list[str]:
 
 def denoise_symbols() -> list[str]:
     return list(_SIGS_DENOISE)
+
+
+def reproject_symbols() -> list[str]:
+    return list(_SIGS_REPROJECT)
 
 
 def check(status: int, func: str) -> None:

@@ -29,6 +29,21 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_color": 1.0,
                     "sigma_position": 0.5}
 
 
+# ComputeShaderPipeline.reproject's defaults: rt_reproject_params_default's
+REPROJECT_DEFAULTS = {"max_history": 64, "position_tolerance2": 1e-5, "lambertian_only": True}
+
+
+def reproject_basis(camera: SceneCamera) -> np.ndarray:
+    """rt_reproject_basis: the 3 x 3 float32 rows that take a world point's offset from
+    camera.center to (a, b, c), the point lying on the view's ray through sample position
+    (a / c, b / c) at c > 0 (rt_reproject.h).  Host only; raises RtError for a degenerate
+    camera."""
+    out = np.zeros(9, np.float32)
+    cam = camera.to_c()
+    _lib.call("rt_reproject_basis", ctypes.byref(cam), _np_ptr(out))
+    return out.reshape(3, 3)
+
+
 def inv_sigma2(sigma: float) -> float:
     """1 / sigma^2 in float32, as denoise passes a sigma to rt_denoise (inf for sigma 0,
     which the library refuses; 0 for an infinite sigma: that weight term is off)."""
@@ -573,6 +588,57 @@ class ComputeShaderPipeline:
                   _ptr(scratch) if scratch is not None else None, width, height,
                   _ptr(guides["hit"]), _ptr(guides["normal"]),
                   _ptr(ids) if ids is not None else None, ctypes.byref(params), self._stream())
+        return out
+
+    # ---- reprojection (rt_reproject.h) ---------------------------------------------------
+    def reproject(self, prev_image: torch.Tensor, width: int, height: int,
+                  prev_camera: SceneCamera, prev_guides: dict, guides: dict, *,
+                  max_history: int = REPROJECT_DEFAULTS["max_history"],
+                  position_tolerance2: float = REPROJECT_DEFAULTS["position_tolerance2"],
+                  lambertian_only: bool = REPROJECT_DEFAULTS["lambertian_only"],
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """rt_reproject: carries `prev_image`, the accumulator of the view `prev_camera`
+        (left as it is), into the current view of the same scene.  prev_guides holds
+        trace_aov's "sphere_id" and "hit" for the previous view, guides its "sphere_id",
+        "hit", "normal" and, with lambertian_only, "material" for the current one.  Each pixel
+        of `out` (allocated when not given; returned) gets the colour and the sample count,
+        capped at max_history, of the previous pixels that saw the same surface point, or
+        zeros (a restart) where none did: pass it to update / update_frames with
+        camera_has_moved = 0, or to denoise.  Every bit equals the NumPy restatement in
+        tests/test_reproject.py.  Enqueued on torch's current stream."""
+        need = width * height * 4
+
+        def image_like(t, what, dtype=torch.float32, n=need):
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) {dtype} tensor of at "
+                                 f"least {n} elements")
+            return t
+
+        image_like(prev_image, "prev_image")
+        names = ("sphere_id", "hit", "normal") + (("material",) if lambertian_only else ())
+        missing = [f"prev_guides[{k!r}]" for k in ("sphere_id", "hit")
+                   if prev_guides.get(k) is None]
+        missing += [f"guides[{k!r}]" for k in names if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"missing {missing} (the planes of trace_aov)")
+        c = _lib.ReprojectPlanesC()
+        for field, src, k in [("prev_sphere_id", prev_guides, "sphere_id"),
+                              ("prev_hit", prev_guides, "hit")] + \
+                             [(k, guides, k) for k in names]:
+            is_id = k == "sphere_id"
+            what = ("prev_guides" if src is prev_guides else "guides") + f"[{k!r}]"
+            t = image_like(src[k], what, torch.int32 if is_id else torch.float32,
+                           width * height if is_id else need)
+            setattr(c, field, t.data_ptr())
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=self.torch_device)
+        image_like(out, "out")
+        params = _lib.ReprojectParamsC(int(max_history), 1 if lambertian_only else 0,
+                                       float(position_tolerance2), 0)
+        cam = prev_camera.to_c()
+        _lib.call("rt_reproject", self._ctx, _ptr(prev_image), _ptr(out), width, height,
+                  ctypes.byref(cam), ctypes.byref(c), ctypes.byref(params), self._stream())
         return out
 
     def present(self, image: torch.Tensor, width: int, height: int,
