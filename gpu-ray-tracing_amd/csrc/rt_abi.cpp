@@ -26,6 +26,8 @@
 #include "rt_selftest_roots.h"
 #include "rt_denoise_kernels.h"
 #include "rt_reproject_kernels.h"
+#include "rt_variance.h"
+#include "rt_variance_kernels.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -1888,6 +1890,115 @@ rt_status rt_reproject(rt_ctx* ctx, const float* prev, float* dst, uint32_t w, u
     forget_count(ctx, dst);
     hipError_t e = rtk::launch_reproject(p, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "rt_reproject_kernel launch");
+    return RT_OK;
+}
+
+void rt_variance_filter_params_default(rt_variance_filter_params* p) {
+    if (!p) return;
+    p->iterations = 5u;
+    p->normal_power_log2 = 5u;
+    p->inv_sigma_luminance2 = 1.0f;
+    p->inv_sigma_position2 = 4.0f;
+    p->min_history = 4u;
+    p->fallback_variance = 1.0f;
+}
+
+// One launch (rt_variance.hip).  Of the context only the device is used.
+rt_status rt_moments_update(rt_ctx* ctx, const float* in, const float* out, float* moments,
+                            uint32_t w, uint32_t h, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!in || !out || !moments)
+        return fail(RT_ERR_INVALID_ARGUMENT, "NULL in_rgba, out_rgba or moments");
+    if (in == out || moments == in || moments == out)
+        return fail(RT_ERR_INVALID_ARGUMENT, "two of in_rgba, out_rgba and moments are equal");
+    if (rt_status s = check_image(w, h)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    rtk::MomentsParams p;
+    p.in = reinterpret_cast<const float4*>(in);
+    p.out = reinterpret_cast<const float4*>(out);
+    p.moments = reinterpret_cast<float4*>(moments);
+    p.width = w;
+    p.height = h;
+    hipError_t e = rtk::launch_moments_update(p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "rt_moments_update_kernel launch");
+    return RT_OK;
+}
+
+// One launch per iteration (rt_variance.hip), rt_denoise's scheme: iteration i writes dst and
+// variance when the number of iterations after it is even, scratch and variance_scratch when
+// it is odd; src and moments are read by iteration 0 alone, which computes v0 as it loads.
+// RT_DENOISE_ROUTE=direct (environment, diagnostic) takes the direct route at every step.
+rt_status rt_variance_filter(rt_ctx* ctx, const float* src, float* dst, float* scratch,
+                             const float* moments, float* variance, float* variance_scratch,
+                             uint32_t w, uint32_t h, const float* hit, const float* normal,
+                             const uint32_t* sphere_id, const rt_variance_filter_params* params,
+                             void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!src || !dst || !moments || !variance || !hit || !normal || !params)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "NULL src, dst, moments, variance, hit, normal or params");
+    if (dst == src || dst == moments)
+        return fail(RT_ERR_INVALID_ARGUMENT, "dst is src or moments");
+    if (variance == src || variance == dst || variance == moments)
+        return fail(RT_ERR_INVALID_ARGUMENT, "variance is src, dst or moments");
+    const uint32_t n = params->iterations;
+    if (n < 1u || n > RT_VARIANCE_MAX_ITERATIONS)
+        return fail(RT_ERR_INVALID_ARGUMENT, "iterations outside 1..RT_VARIANCE_MAX_ITERATIONS");
+    if (params->normal_power_log2 > 10u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "normal_power_log2 above 10");
+    if (params->min_history < 1u || params->min_history > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
+    const float il = params->inv_sigma_luminance2, ip = params->inv_sigma_position2;
+    const float fb = params->fallback_variance;
+    if (!(il >= 0.0f) || !(ip >= 0.0f) || !(fb >= 0.0f) || std::isinf(il) || std::isinf(ip) ||
+        std::isinf(fb))
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "a sigma term or fallback_variance is negative, NaN or infinite");
+    if (n >= 2u) {
+        if (!scratch || scratch == src || scratch == dst || scratch == moments ||
+            scratch == variance)
+            return fail(RT_ERR_INVALID_ARGUMENT,
+                        "iterations >= 2 need a scratch image of their own");
+        if (!variance_scratch || variance_scratch == src || variance_scratch == dst ||
+            variance_scratch == scratch || variance_scratch == moments ||
+            variance_scratch == variance)
+            return fail(RT_ERR_INVALID_ARGUMENT,
+                        "iterations >= 2 need a variance_scratch plane of their own");
+    }
+    if (rt_status s = check_image(w, h)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    const char* env = std::getenv("RT_DENOISE_ROUTE");
+    const bool direct = env && !std::strcmp(env, "direct");
+    rtk::VarianceParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.hit = reinterpret_cast<const float4*>(hit);
+    p.normal = reinterpret_cast<const float4*>(normal);
+    p.id = sphere_id;
+    p.width = w;
+    p.height = h;
+    p.npow = params->normal_power_log2;
+    p.il = il;
+    p.ip = ip;
+    p.min_history = (float)params->min_history;
+    p.fallback = fb;
+    p.in = reinterpret_cast<const float4*>(src);
+    p.moments = reinterpret_cast<const float4*>(moments);
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool last = (n - 1u - i) % 2u == 0u;
+        p.out = reinterpret_cast<float4*>(last ? dst : scratch);
+        p.vout = last ? variance : variance_scratch;
+        p.shift = i;
+        const rtk::VarianceRoute route = !direct && (1u << i) <= rtk::kVarianceRowsMaxStep
+                                             ? rtk::kVarianceRows
+                                             : rtk::kVarianceDirect;
+        hipError_t e = rtk::launch_variance_filter(p, route, static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return hip_fail(e, "rt_variance_filter_kernel launch");
+        p.in = p.out;
+        p.vin = p.vout;
+        p.moments = nullptr;
+    }
     return RT_OK;
 }
 

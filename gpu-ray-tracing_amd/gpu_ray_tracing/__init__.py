@@ -8,7 +8,7 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (DENOISE_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
+from .compute_shader import (DENOISE_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
                              ComputeShaderImages, ComputeShaderNode,
                              ComputeShaderPipeline, chain_schedule, partition_bands,
                              reproject_basis, srgb_thresholds,
@@ -23,6 +23,8 @@ AOV_PLANES = _lib.AOV_PLANES
 RT_AOV_MISS = _lib.RT_AOV_MISS
 # the denoiser (include/rt_denoise.h): ComputeShaderPipeline.denoise's default parameters
 RT_DENOISE_MAX_ITERATIONS = _lib.RT_DENOISE_MAX_ITERATIONS
+# moments and the variance-guided filter (include/rt_variance.h)
+RT_VARIANCE_MAX_ITERATIONS = _lib.RT_VARIANCE_MAX_ITERATIONS
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
@@ -31,4 +33,5 @@ __all__ = [
     "SCENE_THREE", "SCENE_DEFAULT", "SCENE_N", "srgb_thresholds", "image_io",
     "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
+    "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS",
 ]

@@ -215,6 +215,21 @@ class ReprojectPlanesC(ctypes.Structure):
                 ("normal", P), ("material", P)]
 
 
+# include/rt_variance.h (luminance moments and the variance-guided filter)
+_SIGS_VARIANCE = {
+    "rt_variance_filter_params_default": (None, [P]),
+    "rt_moments_update": (ctypes.c_int, [P, P, P, P, U32, U32, P]),
+    "rt_variance_filter": (ctypes.c_int, [P, P, P, P, P, P, P, U32, U32, P, P, P, P, P]),
+}
+RT_VARIANCE_MAX_ITERATIONS = 8
+
+
+class VarianceFilterParamsC(ctypes.Structure):
+    """rt_variance_filter_params (rt_variance.h), 24 bytes."""
+    _fields_ = [("iterations", U32), ("normal_power_log2", U32), ("inv_sigma_luminance2", F),
+                ("inv_sigma_position2", F), ("min_history", U32), ("fallback_variance", F)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -259,7 +274,8 @@ def lib() -> ctypes.CDLL:
                                f"`make -C {PKG_ROOT}` (no CPU fallback exists)")
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
-                                  **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT}.items():
+                                  **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
+                                  **_SIGS_VARIANCE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -318,6 +334,10 @@ def denoise_symbols() -> list[str]:
 
 def reproject_symbols() -> list[str]:
     return list(_SIGS_REPROJECT)
+
+
+def variance_symbols() -> list[str]:
+    return list(_SIGS_VARIANCE)
 
 
 def check(status: int, func: str) -> None:

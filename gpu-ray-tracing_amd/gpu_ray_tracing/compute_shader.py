@@ -33,6 +33,11 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_color": 1.0,
 REPROJECT_DEFAULTS = {"max_history": 64, "position_tolerance2": 1e-5, "lambertian_only": True}
 
 
+# ComputeShaderPipeline.denoise_guided's defaults: rt_variance_filter_params_default's
+GUIDED_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_luminance": 1.0,
+                   "sigma_position": 0.5, "min_history": 4, "fallback_variance": 1.0}
+
+
 def reproject_basis(camera: SceneCamera) -> np.ndarray:
     """rt_reproject_basis: the 3 x 3 float32 rows that take a world point's offset from
     camera.center to (a, b, c), the point lying on the view's ray through sample position
@@ -640,6 +645,91 @@ class ComputeShaderPipeline:
         _lib.call("rt_reproject", self._ctx, _ptr(prev_image), _ptr(out), width, height,
                   ctypes.byref(cam), ctypes.byref(c), ctypes.byref(params), self._stream())
         return out
+
+    # ---- moments and the variance-guided filter (rt_variance.h) --------------------------
+    def moments_update(self, inp: torch.Tensor, out: torch.Tensor, moments: torch.Tensor,
+                       width: int, height: int) -> torch.Tensor:
+        """rt_moments_update: folds the sample that one update added between its input image
+        `inp` and its output image `out` (both left as they are) into `moments`, an image
+        (m1, m2, 0, k) of the running means of luminance and luminance^2 and their sample
+        count, rewritten in place and returned.  Start from zeros (new_image); reproject
+        carries a moments image across a camera move like an accumulator.  Enqueued on torch's
+        current stream."""
+        for t, what in ((inp, "inp"), (out, "out"), (moments, "moments")):
+            _check_image(t, width, height, what)
+        _lib.call("rt_moments_update", self._ctx, _ptr(inp), _ptr(out), _ptr(moments), width,
+                  height, self._stream())
+        return moments
+
+    def denoise_guided(self, image: torch.Tensor, width: int, height: int, guides: dict,
+                       moments: torch.Tensor, *,
+                       iterations: int = GUIDED_DEFAULTS["iterations"],
+                       normal_power_log2: int = GUIDED_DEFAULTS["normal_power_log2"],
+                       sigma_luminance: float = GUIDED_DEFAULTS["sigma_luminance"],
+                       sigma_position: float = GUIDED_DEFAULTS["sigma_position"],
+                       min_history: int = GUIDED_DEFAULTS["min_history"],
+                       fallback_variance: float = GUIDED_DEFAULTS["fallback_variance"],
+                       use_ids: bool = True, out: torch.Tensor | None = None,
+                       scratch: torch.Tensor | None = None,
+                       variance: torch.Tensor | None = None,
+                       variance_scratch: torch.Tensor | None = None
+                       ) -> tuple[torch.Tensor, torch.Tensor]:
+        """rt_variance_filter: denoise's filter with a luminance term scaled by each pixel's
+        own variance, from `moments` (moments_update's image for `image`), and taps weighted by
+        their sample counts (rt_variance.h).  Guides and sigmas as in denoise (sigma_luminance
+        is in units of the local standard deviation and does not change with the iteration).
+        `out`, `variance` ((height, width) float32) and, from two iterations on, `scratch` and
+        `variance_scratch` are allocated when not given; returns (out, variance), the filtered
+        image and the variance of its luminance.  Every bit equals the NumPy restatement in
+        tests/test_variance.py.  Enqueued on torch's current stream."""
+        need = width * height * 4
+
+        def image_like(t, what, dtype=torch.float32, n=need):
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) {dtype} tensor of at "
+                                 f"least {n} elements")
+            return t
+
+        image_like(image, "image")
+        image_like(moments, "moments")
+        names = ("hit", "normal") + (("sphere_id",) if use_ids else ())
+        missing = [k for k in names if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"guides lacks {missing} (the planes of trace_aov)")
+        image_like(guides["hit"], 'guides["hit"]')
+        image_like(guides["normal"], 'guides["normal"]')
+        ids = None
+        if use_ids:
+            ids = image_like(guides["sphere_id"], 'guides["sphere_id"]', torch.int32,
+                             width * height)
+        dev = self.torch_device
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        if variance is None:
+            variance = torch.empty((height, width), dtype=torch.float32, device=dev)
+        if iterations >= 2:
+            if scratch is None:
+                scratch = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+            if variance_scratch is None:
+                variance_scratch = torch.empty((height, width), dtype=torch.float32, device=dev)
+        image_like(out, "out")
+        image_like(variance, "variance", n=width * height)
+        if scratch is not None:
+            image_like(scratch, "scratch")
+        if variance_scratch is not None:
+            image_like(variance_scratch, "variance_scratch", n=width * height)
+        params = _lib.VarianceFilterParamsC(int(iterations), int(normal_power_log2),
+                                            inv_sigma2(sigma_luminance),
+                                            inv_sigma2(sigma_position), int(min_history),
+                                            float(fallback_variance))
+        _lib.call("rt_variance_filter", self._ctx, _ptr(image), _ptr(out),
+                  _ptr(scratch) if scratch is not None else None, _ptr(moments),
+                  _ptr(variance),
+                  _ptr(variance_scratch) if variance_scratch is not None else None,
+                  width, height, _ptr(guides["hit"]), _ptr(guides["normal"]),
+                  _ptr(ids) if ids is not None else None, ctypes.byref(params), self._stream())
+        return out, variance
 
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:
