@@ -32,6 +32,7 @@ LIB = ROOT / "gpu-ray-tracing_amd" / "build" / "librt_hip.so"
 F32 = np.float32
 FLT_MAX = np.finfo(np.float32).max
 W, H = 37, 21                 # a partial 64x4 tile both ways; lower than the reach of step 16's taps
+#                               (tests/test_post_shapes.py has the shapes beyond one workgroup)
 MISS = -1
 RT_ERR_INVALID_ARGUMENT, RT_ERR_INVALID_SIZE, RT_ERR_INVALID_CONTEXT = 1, 2, 6
 SENT = -12345.0
