@@ -28,6 +28,8 @@
 #include "rt_reproject_kernels.h"
 #include "rt_variance.h"
 #include "rt_variance_kernels.h"
+#include "rt_adaptive.h"
+#include "rt_adaptive_kernels.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -2000,6 +2002,116 @@ rt_status rt_variance_filter(rt_ctx* ctx, const float* src, float* dst, float* s
         p.moments = nullptr;
     }
     return RT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Shared body of rt_update_adaptive / rt_update_adaptive_bands (rt_adaptive.h): the argument
+// checks, then prepare() as every trace launch (scene upload, hash tables, candidate lists) and
+// one rt_adaptive_kernel launch over the band set.  The instance follows the context as
+// trace_kernel_for does, with ray_color's culled scans in place of the bounce instance at
+// max_depth >= 2.  No hint, no tile order, no cost recording, no launch info.
+rt_status update_adaptive(rt_ctx* ctx, const float* in, float* out, const float* error,
+                          uint64_t* tile_mask, uint32_t w, uint32_t h, const rt_band_set& bs,
+                          const rt_scene_camera* cam, const rt_sphere* spheres, uint32_t count,
+                          const rt_adaptive_params* params, void* stream_v) {
+    if (!in || !out || !error || !cam || !params)
+        return fail(RT_ERR_INVALID_ARGUMENT, "NULL in_rgba, out_rgba, error, camera or params");
+    if (out == in || static_cast<const void*>(out) == error ||
+        static_cast<const void*>(out) == tile_mask)
+        return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is in_rgba, error or tile_mask");
+    if (params->min_samples > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
+    const float at2 = params->abs_tolerance2, rt2 = params->rel_tolerance2;
+    if (!(at2 >= 0.0f) || !(rt2 >= 0.0f) || std::isinf(at2) || std::isinf(rt2))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
+    if (rt_status s = check_image(w, h)) return s;
+    if (rt_status s = check_band_set(h, bs)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const float seed = cam->random_seed;
+    rtk::TraceParams p;
+    if (rt_status s = prepare(ctx, in, out, w, h, bs, cam, spheres, count, &seed, stream, p))
+        return s;
+    if (bs.count == 0) return RT_OK;
+    p.in = reinterpret_cast<const float4*>(in);
+    p.out = reinterpret_cast<float4*>(out);
+    p.frames = 1u;
+    p.reset_first = cam->camera_has_moved > 0.5f ? 1u : 0u;
+    p.seed_b[0] = host_f2u(seed * 4294967296.0f);
+    p.lds_records = 0u;              // (the culled scans read the records from L2)
+    const int auto_kernel = trace_kernel_for(ctx, p);
+    const int kernel = auto_kernel == rtk::kTraceBounce ? rtk::kTraceCulled : auto_kernel;
+    rtk::AdaptiveParams a;
+    a.error = error;
+    a.tile_mask = tile_mask;
+    a.min_samples = params->min_samples;
+    a.abs_tolerance2 = at2;
+    a.rel_tolerance2 = rt2;
+    forget_count(ctx, out);          // the counts now differ per pixel
+    hipError_t e = rtk::launch_adaptive(p, a, kernel, stream);
+    if (e != hipSuccess) return hip_fail(e, "rt_adaptive_kernel launch");
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rt_adaptive_params_default(rt_adaptive_params* p) {
+    if (!p) return;
+    p->min_samples = 16u;
+    p->abs_tolerance2 = 1e-5f;
+    p->rel_tolerance2 = 2.5e-4f;
+}
+
+// One launch (rt_adaptive.hip).  Of the context only the device is used.
+rt_status rt_adaptive_error(rt_ctx* ctx, const float* image, const float* moments, float* error,
+                            uint32_t w, uint32_t h, uint32_t min_history, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!image || !moments || !error)
+        return fail(RT_ERR_INVALID_ARGUMENT, "NULL image, moments or error");
+    if (error == image || error == moments)
+        return fail(RT_ERR_INVALID_ARGUMENT, "error is image or moments");
+    if (min_history < 1u || min_history > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
+    if (rt_status s = check_image(w, h)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    rtk::AdaptiveErrorParams p;
+    p.image = reinterpret_cast<const float4*>(image);
+    p.moments = reinterpret_cast<const float4*>(moments);
+    p.error = error;
+    p.width = w;
+    p.height = h;
+    p.min_history = (float)min_history;
+    hipError_t e = rtk::launch_adaptive_error(p, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "rt_adaptive_error_kernel launch");
+    return RT_OK;
+}
+
+rt_status rt_update_adaptive_bands(rt_ctx* ctx, const float* in, float* out, const float* error,
+                                   uint64_t* tile_mask, uint32_t w, uint32_t h,
+                                   const rt_band_set* bands, const rt_scene_camera* cam,
+                                   const rt_sphere* spheres, uint32_t count,
+                                   const rt_adaptive_params* params, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!bands) return fail(RT_ERR_INVALID_ARGUMENT, "bands is NULL");
+    return update_adaptive(ctx, in, out, error, tile_mask, w, h, *bands, cam, spheres, count,
+                           params, stream);
+}
+
+rt_status rt_update_adaptive(rt_ctx* ctx, const float* in, float* out, const float* error,
+                             uint64_t* tile_mask, uint32_t w, uint32_t h,
+                             const rt_scene_camera* cam, const rt_sphere* spheres,
+                             uint32_t count, const rt_adaptive_params* params, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    const rt_band_set all = stripe_set(h, 0, 1);    // (h is checked below, before the set is)
+    return update_adaptive(ctx, in, out, error, tile_mask, w, h, all, cam, spheres, count, params,
+                           stream);
 }
 
 }  // extern "C"

@@ -295,6 +295,18 @@ struct AovParams {
 };
 // waves tx0 .. tx0 + tiles_x - 1 of local bands [0, bands): one wave per 8x8 tile
 hipError_t launch_aov(const AovParams& p, uint32_t tiles_x, uint32_t bands, hipStream_t stream);
+// Adaptive sampling (rt_adaptive.h; rt_kernels.hip rt_adaptive_kernel): one update over p's
+// image and stripes in which a pixel takes a sample only while its error is above the tolerance.
+struct AdaptiveParams {
+    const float* error;        // per pixel of the local image: the estimated error
+    uint64_t* tile_mask;       // per local tile: the lanes that were sampled (null: not wanted)
+    uint32_t min_samples;
+    float abs_tolerance2, rel_tolerance2;
+};
+// p: one frame (frames 1, seed_b[0]), no hint, lds_records 0; kernel: kTraceExhaustive,
+// kTraceList or kTraceCulled
+hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int kernel,
+                           hipStream_t stream);
 const char* trace_kernel_name();
 // "rt_single_kernel<p>": p = pix tiles per wave (0: kTraceSingle's)
 const char* single_kernel_name(uint32_t pix);

@@ -4037,6 +4037,85 @@ hipError_t launch_aov(const AovParams& p, uint32_t tiles_x, uint32_t bands, hipS
     return hipGetLastError();
 }
 
+// ---- Adaptive sampling (rt_adaptive.h) -----------------------------------------------
+//
+// One `update` in which only the pixels whose error estimate is still above the tolerance
+// take a sample.  One wave per 8x8 tile on rt_trace_kernel's stripe map (tile_coord), four
+// tiles of a band per workgroup.  The wave loads its accumulator texels and error values,
+// decides per lane (rt_adaptive.h: the reset, min_samples, the tolerance, the spp cap), forms
+// the tile's mask with one ballot and lane 0 stores the word.  A wave whose ballot is empty
+// writes its texels back as they pass through and ends: it reads no candidate list, hash table
+// or sphere record.  Any other wave traces one sample with the mask as the per-lane `live` flag
+// — trace_pixel's mechanism for n < spp — through sample<kScan> and ray_color as they are,
+// without a sample-count hint (uni = false: the counts differ per pixel), and accumulates with
+// the reference's IEEE division (wgsl:356), so a sampled texel has rt_update's bits.
+// kScan: kTraceExhaustive, kTraceList (depth <= 1, camera in the proven domain: the fast
+// cores) or kTraceCulled (candidate lists for camera rays, cone / grid culling for bounce rays
+// in ray_color; no LDS copy of the records: TraceParams::lds_records is 0 here).
+template <int kScan>
+__global__ __launch_bounds__(256, RT_TRACE_MIN_WAVES) void rt_adaptive_kernel(
+    const TraceParams p, const AdaptiveParams a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t tiles_x = (p.width + 7u) >> 3;
+    const uint32_t tx = blockIdx.x * 4u + wave;
+    if (tx >= tiles_x) return;                                    // whole wave exits
+    const uint32_t lband = blockIdx.y;
+    const TileCoord tc = tile_coord(p, tx, lband, lane);
+    const uint32_t tile = lband * tiles_x + tx;
+    // (a lane off the image reads texel 0 of the local buffers and stores nothing)
+    const size_t at = tc.valid ? tc.idx : 0;
+    const float4 I = p.in[at];
+    const float err = a.error[at];
+    const uint32_t spp = p.spp;                                   // wgsl:343
+    v3 c = mk(0.0f, 0.0f, 0.0f);
+    uint32_t n = 0u;
+    bool sampled = 0u < spp;                                      // a reset: wgsl:345-350
+    if (!p.reset_first) {
+        c = mk(I.x, I.y, I.z);                                    // wgsl:339-341
+        n = f2u(I.w);
+        const float lm = (0.2126f * I.x + 0.7152f * I.y) + 0.0722f * I.z;
+        const float thr = a.abs_tolerance2 + a.rel_tolerance2 * (lm * lm);
+        const bool converged = n >= a.min_samples && err <= thr;  // (a NaN: not converged)
+        sampled = n < spp && !converged;
+    }
+    sampled = sampled && tc.valid;
+    const uint64_t m = rt_ballot(sampled);
+    if (a.tile_mask && lane == 0u) a.tile_mask[tile] = m;
+    if (m != 0ull) {
+        const uint32_t ncand =
+            (kScan != kTraceExhaustive && p.cand) ? load_cnt(p.cand, tile) : kCandNone;
+        const uint32_t hxy =
+            p.hx[min(tc.x, p.width - 1u)] ^ p.hy[min(tc.y, p.height - 1u)];
+        const Cam cam = cam_params(p);
+        const v3 col = sample<kScan>(p, cam, tile, ncand, tc, hxy, n, p.seed_b[0], 0u, sampled,
+                                     false);
+        if (sampled) {
+            const float k = (float)(n + 1u);                      // wgsl:356
+            c = mk(c.x + (col.x - c.x) / k, c.y + (col.y - c.y) / k, c.z + (col.z - c.z) / k);
+            n += 1u;
+        }
+    }
+    // wgsl:362-363; a texel that passes through is what spp = 0 would write: u32(alpha) again
+    if (tc.valid) p.out[tc.idx] = make_float4(c.x, c.y, c.z, (float)n);
+}
+
+hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int kernel,
+                           hipStream_t stream) {
+    const dim3 grid = tile_grid(p);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    if (kernel == kTraceList)
+        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceList>, grid, dim3(256), 0, stream, p, a);
+    else if (kernel == kTraceCulled)
+        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceCulled>, grid, dim3(256), 0, stream, p, a);
+    else if (kernel == kTraceExhaustive)
+        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceExhaustive>, grid, dim3(256), 0, stream, p,
+                           a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 const char* trace_kernel_name() { return "rt_trace_kernel"; }
 const char* single_kernel_name(uint32_t pix) {
     static const char* const names[] = {"rt_single_kernel<1>", "rt_single_kernel<2>",

@@ -8,7 +8,7 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (DENOISE_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
+from .compute_shader import (ADAPTIVE_DEFAULTS, DENOISE_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
                              ComputeShaderImages, ComputeShaderNode,
                              ComputeShaderPipeline, chain_schedule, partition_bands,
                              reproject_basis, srgb_thresholds,
@@ -33,5 +33,5 @@ __all__ = [
     "SCENE_THREE", "SCENE_DEFAULT", "SCENE_N", "srgb_thresholds", "image_io",
     "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
-    "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS",
+    "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS", "ADAPTIVE_DEFAULTS",
 ]

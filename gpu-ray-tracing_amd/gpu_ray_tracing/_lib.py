@@ -230,6 +230,20 @@ class VarianceFilterParamsC(ctypes.Structure):
                 ("inv_sigma_position2", F), ("min_history", U32), ("fallback_variance", F)]
 
 
+# include/rt_adaptive.h (variance-driven adaptive sampling)
+_SIGS_ADAPTIVE = {
+    "rt_adaptive_params_default": (None, [P]),
+    "rt_adaptive_error": (ctypes.c_int, [P, P, P, P, U32, U32, U32, P]),
+    "rt_update_adaptive": (ctypes.c_int, [P, P, P, P, P, U32, U32, P, P, U32, P, P]),
+    "rt_update_adaptive_bands": (ctypes.c_int, [P, P, P, P, P, U32, U32, P, P, P, U32, P, P]),
+}
+
+
+class AdaptiveParamsC(ctypes.Structure):
+    """rt_adaptive_params (rt_adaptive.h), 12 bytes."""
+    _fields_ = [("min_samples", U32), ("abs_tolerance2", F), ("rel_tolerance2", F)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -275,7 +289,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
-                                  **_SIGS_VARIANCE}.items():
+                                  **_SIGS_VARIANCE, **_SIGS_ADAPTIVE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -338,6 +352,10 @@ def reproject_symbols() -> list[str]:
 
 def variance_symbols() -> list[str]:
     return list(_SIGS_VARIANCE)
+
+
+def adaptive_symbols() -> list[str]:
+    return list(_SIGS_ADAPTIVE)
 
 
 def check(status: int, func: str) -> None:

@@ -38,6 +38,10 @@ GUIDED_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_luminance": 1
                    "sigma_position": 0.5, "min_history": 4, "fallback_variance": 1.0}
 
 
+# ComputeShaderPipeline.update_adaptive's defaults: rt_adaptive_params_default's
+ADAPTIVE_DEFAULTS = {"min_samples": 16, "abs_tolerance2": 1e-5, "rel_tolerance2": 2.5e-4}
+
+
 def reproject_basis(camera: SceneCamera) -> np.ndarray:
     """rt_reproject_basis: the 3 x 3 float32 rows that take a world point's offset from
     camera.center to (a, b, c), the point lying on the view's ray through sample position
@@ -92,6 +96,14 @@ def _check_image(t: torch.Tensor, width: int, height: int, name: str) -> None:
         raise ValueError(f"{name} must be contiguous float32")
     if t.numel() < width * height * 4:
         raise ValueError(f"{name} holds {t.numel()} floats, need {width * height * 4}")
+
+
+def _check_plane(t, n: int, dtype, name: str):
+    if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+            or not t.is_contiguous() or t.numel() < n):
+        raise ValueError(f"{name} must be a contiguous CUDA (HIP) {dtype} tensor of at least "
+                         f"{n} elements")
+    return t
 
 
 def stripe_local_rows(height: int, rank: int, nranks: int) -> int:
@@ -730,6 +742,62 @@ class ComputeShaderPipeline:
                   width, height, _ptr(guides["hit"]), _ptr(guides["normal"]),
                   _ptr(ids) if ids is not None else None, ctypes.byref(params), self._stream())
         return out, variance
+
+    # ---- adaptive sampling (rt_adaptive.h) -----------------------------------------------
+    def adaptive_error(self, image: torch.Tensor, moments: torch.Tensor, width: int,
+                       height: int, *, min_history: int = 4,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+        """rt_adaptive_error: the error plane update_adaptive reads, a (height, width) float32
+        tensor (`out`, allocated when not given; returned): the variance of the mean of each
+        pixel's luminance from `moments` (moments_update's image for the accumulator `image`),
+        +inf where the moments hold fewer than min_history samples.  Both inputs are left as
+        they are.  Enqueued on torch's current stream."""
+        _check_image(image, width, height, "image")
+        _check_image(moments, width, height, "moments")
+        if out is None:
+            out = torch.empty((height, width), dtype=torch.float32, device=self.torch_device)
+        _check_plane(out, width * height, torch.float32, "out")
+        _lib.call("rt_adaptive_error", self._ctx, _ptr(image), _ptr(moments), _ptr(out), width,
+                  height, int(min_history), self._stream())
+        return out
+
+    def update_adaptive(self, inp: torch.Tensor, out: torch.Tensor, width: int, height: int,
+                        camera: SceneCamera, spheres: SphereCollection, error: torch.Tensor, *,
+                        min_samples: int = ADAPTIVE_DEFAULTS["min_samples"],
+                        abs_tolerance2: float = ADAPTIVE_DEFAULTS["abs_tolerance2"],
+                        rel_tolerance2: float = ADAPTIVE_DEFAULTS["rel_tolerance2"],
+                        tile_mask=False, bands=None) -> torch.Tensor | None:
+        """rt_update_adaptive / rt_update_adaptive_bands: one `update` from `inp` into `out` in
+        which a pixel takes a sample only while it has fewer than min_samples samples or its
+        `error` (adaptive_error's plane, or denoise_guided's variance) is above abs_tolerance2 +
+        rel_tolerance2 * luminance^2; every other pixel passes through.  A sampled pixel has
+        update's bits.  tile_mask: True (allocated) or an int64 tensor of one word per 8 x 8
+        tile, tile rows first, bit (y & 7) * 8 + (x & 7) set where pixel (x, y) was sampled;
+        it is returned (else None).  bands = (first, step, count): compact local buffers of
+        count * 8 rows with global pixel coordinates, as update_frames_bands.  Enqueued on
+        torch's current stream."""
+        rows = height if bands is None else int(bands[2]) * RT_STRIPE_ROWS
+        _check_image(inp, width, rows, "in")
+        _check_image(out, width, rows, "out")
+        _check_plane(error, width * rows, torch.float32, "error")
+        tiles = ((width + 7) // 8) * ((rows + 7) // 8)
+        mask = None
+        if tile_mask is True:
+            mask = torch.empty((tiles,), dtype=torch.int64, device=self.torch_device)
+        elif tile_mask is not False and tile_mask is not None:
+            mask = _check_plane(tile_mask, tiles, torch.int64, "tile_mask")
+        params = _lib.AdaptiveParamsC(int(min_samples), float(abs_tolerance2),
+                                      float(rel_tolerance2))
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        head = (self._ctx, _ptr(inp), _ptr(out), _ptr(error),
+                _ptr(mask) if mask is not None else None, width, height)
+        tail = (ctypes.byref(cam), p, n, ctypes.byref(params), self._stream())
+        if bands is None:
+            _lib.call("rt_update_adaptive", *head, *tail)
+        else:
+            _lib.call("rt_update_adaptive_bands", *head, _lib.band_sets([bands]), *tail)
+        return mask
 
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:
