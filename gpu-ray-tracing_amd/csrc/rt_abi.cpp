@@ -9,7 +9,6 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,15 +20,8 @@
 #include "rt_abi.h"
 #include "rt_aov.h"
 #include "rt_chain_parts.h"
-#include "rt_denoise.h"
-#include "rt_reproject.h"
 #include "rt_selftest_roots.h"
-#include "rt_denoise_kernels.h"
-#include "rt_reproject_kernels.h"
-#include "rt_variance.h"
-#include "rt_variance_kernels.h"
 #include "rt_adaptive.h"
-#include "rt_adaptive_kernels.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -187,6 +179,14 @@ rt_status check_image(uint32_t w, uint32_t h) {
 
 int ctx_device(const rt_ctx* ctx) { return ctx->device; }
 
+void forget_count(rt_ctx* ctx, const void* image) {
+    for (size_t i = 0; i < ctx->counts.size(); ++i)
+        if (ctx->counts[i].image == image) {
+            ctx->counts.erase(ctx->counts.begin() + (long)i);
+            return;
+        }
+}
+
 }  // namespace rti
 
 namespace {
@@ -194,6 +194,7 @@ namespace {
 using rti::check_image;
 using rti::DeviceGuard;
 using rti::fail;
+using rti::forget_count;
 using rti::hip_fail;
 
 constexpr uint32_t kMaxSpheres = 1u << 20;
@@ -1018,14 +1019,6 @@ bool lookup_count(const rt_ctx* ctx, const void* image, const rtk::TraceParams& 
     return false;
 }
 
-void forget_count(rt_ctx* ctx, const void* image) {
-    for (size_t i = 0; i < ctx->counts.size(); ++i)
-        if (ctx->counts[i].image == image) {
-            ctx->counts.erase(ctx->counts.begin() + (long)i);
-            return;
-        }
-}
-
 void record_count(rt_ctx* ctx, const void* image, const rtk::TraceParams& p, uint32_t n) {
     forget_count(ctx, image);
     if (ctx->counts.size() >= 16) ctx->counts.erase(ctx->counts.begin());
@@ -1736,274 +1729,6 @@ rt_status rt_pick(rt_ctx* ctx, uint32_t w, uint32_t h, uint32_t x, uint32_t y,
     return RT_OK;
 }
 
-void rt_denoise_params_default(rt_denoise_params* p) {
-    if (!p) return;
-    p->iterations = 5u;
-    p->normal_power_log2 = 5u;
-    p->inv_sigma_color2 = 1.0f;
-    p->inv_sigma_position2 = 4.0f;
-}
-
-// One launch per iteration (rt_denoise.hip).  The last iteration writes dst, so iteration i
-// writes dst when the number of iterations after it is even and scratch when it is odd; src is
-// read by iteration 0 alone.  Steps up to 16 stage their texels in LDS, larger steps load every
-// tap from global memory; RT_DENOISE_ROUTE=direct (environment, diagnostic)
-// takes that route at every step.  Of the context only the device is used.
-rt_status rt_denoise(rt_ctx* ctx, const float* src, float* dst, float* scratch, uint32_t w,
-                     uint32_t h, const float* hit, const float* normal, const uint32_t* sphere_id,
-                     const rt_denoise_params* params, void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
-    if (!src || !dst || !hit || !normal || !params)
-        return fail(RT_ERR_INVALID_ARGUMENT, "NULL src, dst, hit, normal or params");
-    if (dst == src) return fail(RT_ERR_INVALID_ARGUMENT, "dst is src");
-    const uint32_t n = params->iterations;
-    if (n < 1u || n > RT_DENOISE_MAX_ITERATIONS)
-        return fail(RT_ERR_INVALID_ARGUMENT, "iterations outside 1..RT_DENOISE_MAX_ITERATIONS");
-    if (params->normal_power_log2 > 10u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "normal_power_log2 above 10");
-    const float ic0 = params->inv_sigma_color2, ip = params->inv_sigma_position2;
-    if (!(ic0 >= 0.0f) || !(ip >= 0.0f) || std::isinf(ic0) || std::isinf(ip))
-        return fail(RT_ERR_INVALID_ARGUMENT, "a sigma term is negative, NaN or infinite");
-    if (n >= 2u && (!scratch || scratch == src || scratch == dst))
-        return fail(RT_ERR_INVALID_ARGUMENT, "iterations >= 2 need a scratch image of their own");
-    if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    const char* env = std::getenv("RT_DENOISE_ROUTE");
-    const bool direct = env && !std::strcmp(env, "direct");
-    rtk::DenoiseParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.hit = reinterpret_cast<const float4*>(hit);
-    p.normal = reinterpret_cast<const float4*>(normal);
-    p.id = sphere_id;
-    p.width = w;
-    p.height = h;
-    p.npow = params->normal_power_log2;
-    p.ip = ip;
-    const float4* in = reinterpret_cast<const float4*>(src);
-    float ic = ic0;                                       // ic0 * 4^i: exact, or +inf
-    for (uint32_t i = 0; i < n; ++i) {
-        float4* out = reinterpret_cast<float4*>((n - 1u - i) % 2u == 0u ? dst : scratch);
-        p.in = in;
-        p.out = out;
-        p.shift = i;
-        p.ic = std::min(ic, FLT_MAX);
-        const rtk::DenoiseRoute route = !direct && (1u << i) <= rtk::kDenoiseRowsMaxStep
-                                            ? rtk::kDenoiseRows
-                                            : rtk::kDenoiseDirect;
-        hipError_t e = rtk::launch_denoise(p, route, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail(e, "rt_denoise_kernel launch");
-        in = out;
-        ic = ic * 4.0f;
-    }
-    return RT_OK;
-}
-
-void rt_reproject_params_default(rt_reproject_params* p) {
-    if (!p) return;
-    p->max_history = 64u;
-    p->lambertian_only = 1u;
-    p->position_tolerance2 = 1e-5f;
-    p->_reserved = 0u;
-}
-
-// The rows of the inverse of [du' dv' e'] in double, each operation as rt_reproject.h states it
-// (this file is built with -ffp-contract=off).
-rt_status rt_reproject_basis(const rt_scene_camera* cam, float out[9]) {
-    if (!cam || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL prev_camera or out");
-    double o[3], du[3], dv[3], e[3];
-    for (int k = 0; k < 3; ++k) {
-        o[k] = (double)cam->center[k];
-        du[k] = (double)cam->pixel_delta_u[k];
-        dv[k] = (double)cam->pixel_delta_v[k];
-        e[k] = (double)cam->viewport_upper_left[k] - o[k];
-    }
-    auto cross = [](const double* a, const double* b, double* r) {
-        r[0] = a[1] * b[2] - a[2] * b[1];
-        r[1] = a[2] * b[0] - a[0] * b[2];
-        r[2] = a[0] * b[1] - a[1] * b[0];
-    };
-    double c[3][3];
-    cross(dv, e, c[0]);
-    cross(e, du, c[1]);
-    cross(du, dv, c[2]);
-    const double det = (du[0] * c[0][0] + du[1] * c[0][1]) + du[2] * c[0][2];
-    if (det == 0.0 || !std::isfinite(det))
-        return fail(RT_ERR_INVALID_ARGUMENT, "degenerate prev_camera: [du dv e] is singular");
-    float rows[9];
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) {
-            rows[3 * i + k] = (float)(c[i][k] / det);
-            if (!std::isfinite(rows[3 * i + k]))
-                return fail(RT_ERR_INVALID_ARGUMENT,
-                            "degenerate prev_camera: the basis is not finite");
-        }
-    std::memcpy(out, rows, sizeof(rows));
-    return RT_OK;
-}
-
-// One launch (rt_reproject.hip).  Of the context the device is used, and dst's uniform-count
-// record is dropped: dst holds per-pixel counts afterwards.
-rt_status rt_reproject(rt_ctx* ctx, const float* prev, float* dst, uint32_t w, uint32_t h,
-                       const rt_scene_camera* prev_camera, const rt_reproject_planes* planes,
-                       const rt_reproject_params* params, void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
-    if (!prev || !dst || !prev_camera || !planes || !params)
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "NULL prev_rgba, dst_rgba, prev_camera, planes or params");
-    if (dst == prev) return fail(RT_ERR_INVALID_ARGUMENT, "dst_rgba is prev_rgba");
-    if (params->max_history < 1u || params->max_history > (1u << 24))
-        return fail(RT_ERR_INVALID_ARGUMENT, "max_history outside 1..16777216");
-    if (params->lambertian_only > 1u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "lambertian_only is neither 0 nor 1");
-    if (params->_reserved != 0u) return fail(RT_ERR_INVALID_ARGUMENT, "_reserved is not 0");
-    const float tol2 = params->position_tolerance2;
-    if (!(tol2 >= 0.0f) || std::isinf(tol2))
-        return fail(RT_ERR_INVALID_ARGUMENT, "position_tolerance2 is negative, NaN or infinite");
-    if (!planes->prev_sphere_id || !planes->prev_hit || !planes->sphere_id || !planes->hit ||
-        !planes->normal || (params->lambertian_only && !planes->material))
-        return fail(RT_ERR_INVALID_ARGUMENT, "a required plane is NULL");
-    if (rt_status s = check_image(w, h)) return s;
-    rtk::ReprojectParams p;
-    std::memset(&p, 0, sizeof(p));
-    float rows[9];
-    if (rt_status s = rt_reproject_basis(prev_camera, rows)) return s;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    p.prev = reinterpret_cast<const float4*>(prev);
-    p.dst = reinterpret_cast<float4*>(dst);
-    p.prev_id = planes->prev_sphere_id;
-    p.prev_hit = reinterpret_cast<const float4*>(planes->prev_hit);
-    p.id = planes->sphere_id;
-    p.hit = reinterpret_cast<const float4*>(planes->hit);
-    p.normal = reinterpret_cast<const float4*>(planes->normal);
-    p.material = params->lambertian_only
-                     ? reinterpret_cast<const float4*>(planes->material) : nullptr;
-    p.width = w;
-    p.height = h;
-    for (int k = 0; k < 3; ++k) {
-        p.r0[k] = rows[k];
-        p.r1[k] = rows[3 + k];
-        p.r2[k] = rows[6 + k];
-        p.o[k] = prev_camera->center[k];
-    }
-    p.tol2 = tol2;
-    p.max_history = (float)params->max_history;
-    forget_count(ctx, dst);
-    hipError_t e = rtk::launch_reproject(p, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "rt_reproject_kernel launch");
-    return RT_OK;
-}
-
-void rt_variance_filter_params_default(rt_variance_filter_params* p) {
-    if (!p) return;
-    p->iterations = 5u;
-    p->normal_power_log2 = 5u;
-    p->inv_sigma_luminance2 = 1.0f;
-    p->inv_sigma_position2 = 4.0f;
-    p->min_history = 4u;
-    p->fallback_variance = 1.0f;
-}
-
-// One launch (rt_variance.hip).  Of the context only the device is used.
-rt_status rt_moments_update(rt_ctx* ctx, const float* in, const float* out, float* moments,
-                            uint32_t w, uint32_t h, void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
-    if (!in || !out || !moments)
-        return fail(RT_ERR_INVALID_ARGUMENT, "NULL in_rgba, out_rgba or moments");
-    if (in == out || moments == in || moments == out)
-        return fail(RT_ERR_INVALID_ARGUMENT, "two of in_rgba, out_rgba and moments are equal");
-    if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    rtk::MomentsParams p;
-    p.in = reinterpret_cast<const float4*>(in);
-    p.out = reinterpret_cast<const float4*>(out);
-    p.moments = reinterpret_cast<float4*>(moments);
-    p.width = w;
-    p.height = h;
-    hipError_t e = rtk::launch_moments_update(p, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "rt_moments_update_kernel launch");
-    return RT_OK;
-}
-
-// One launch per iteration (rt_variance.hip), rt_denoise's scheme: iteration i writes dst and
-// variance when the number of iterations after it is even, scratch and variance_scratch when
-// it is odd; src and moments are read by iteration 0 alone, which computes v0 as it loads.
-// RT_DENOISE_ROUTE=direct (environment, diagnostic) takes the direct route at every step.
-rt_status rt_variance_filter(rt_ctx* ctx, const float* src, float* dst, float* scratch,
-                             const float* moments, float* variance, float* variance_scratch,
-                             uint32_t w, uint32_t h, const float* hit, const float* normal,
-                             const uint32_t* sphere_id, const rt_variance_filter_params* params,
-                             void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
-    if (!src || !dst || !moments || !variance || !hit || !normal || !params)
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "NULL src, dst, moments, variance, hit, normal or params");
-    if (dst == src || dst == moments)
-        return fail(RT_ERR_INVALID_ARGUMENT, "dst is src or moments");
-    if (variance == src || variance == dst || variance == moments)
-        return fail(RT_ERR_INVALID_ARGUMENT, "variance is src, dst or moments");
-    const uint32_t n = params->iterations;
-    if (n < 1u || n > RT_VARIANCE_MAX_ITERATIONS)
-        return fail(RT_ERR_INVALID_ARGUMENT, "iterations outside 1..RT_VARIANCE_MAX_ITERATIONS");
-    if (params->normal_power_log2 > 10u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "normal_power_log2 above 10");
-    if (params->min_history < 1u || params->min_history > (1u << 24))
-        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
-    const float il = params->inv_sigma_luminance2, ip = params->inv_sigma_position2;
-    const float fb = params->fallback_variance;
-    if (!(il >= 0.0f) || !(ip >= 0.0f) || !(fb >= 0.0f) || std::isinf(il) || std::isinf(ip) ||
-        std::isinf(fb))
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "a sigma term or fallback_variance is negative, NaN or infinite");
-    if (n >= 2u) {
-        if (!scratch || scratch == src || scratch == dst || scratch == moments ||
-            scratch == variance)
-            return fail(RT_ERR_INVALID_ARGUMENT,
-                        "iterations >= 2 need a scratch image of their own");
-        if (!variance_scratch || variance_scratch == src || variance_scratch == dst ||
-            variance_scratch == scratch || variance_scratch == moments ||
-            variance_scratch == variance)
-            return fail(RT_ERR_INVALID_ARGUMENT,
-                        "iterations >= 2 need a variance_scratch plane of their own");
-    }
-    if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    const char* env = std::getenv("RT_DENOISE_ROUTE");
-    const bool direct = env && !std::strcmp(env, "direct");
-    rtk::VarianceParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.hit = reinterpret_cast<const float4*>(hit);
-    p.normal = reinterpret_cast<const float4*>(normal);
-    p.id = sphere_id;
-    p.width = w;
-    p.height = h;
-    p.npow = params->normal_power_log2;
-    p.il = il;
-    p.ip = ip;
-    p.min_history = (float)params->min_history;
-    p.fallback = fb;
-    p.in = reinterpret_cast<const float4*>(src);
-    p.moments = reinterpret_cast<const float4*>(moments);
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool last = (n - 1u - i) % 2u == 0u;
-        p.out = reinterpret_cast<float4*>(last ? dst : scratch);
-        p.vout = last ? variance : variance_scratch;
-        p.shift = i;
-        const rtk::VarianceRoute route = !direct && (1u << i) <= rtk::kVarianceRowsMaxStep
-                                             ? rtk::kVarianceRows
-                                             : rtk::kVarianceDirect;
-        hipError_t e = rtk::launch_variance_filter(p, route, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail(e, "rt_variance_filter_kernel launch");
-        p.in = p.out;
-        p.vin = p.vout;
-        p.moments = nullptr;
-    }
-    return RT_OK;
-}
-
 }  // extern "C"
 
 namespace {
@@ -2025,7 +1750,7 @@ rt_status update_adaptive(rt_ctx* ctx, const float* in, float* out, const float*
     if (params->min_samples > (1u << 24))
         return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
     const float at2 = params->abs_tolerance2, rt2 = params->rel_tolerance2;
-    if (!(at2 >= 0.0f) || !(rt2 >= 0.0f) || std::isinf(at2) || std::isinf(rt2))
+    if (!rti::nonneg_finite(at2) || !rti::nonneg_finite(rt2))
         return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
     if (rt_status s = check_image(w, h)) return s;
     if (rt_status s = check_band_set(h, bs)) return s;
@@ -2066,31 +1791,6 @@ void rt_adaptive_params_default(rt_adaptive_params* p) {
     p->min_samples = 16u;
     p->abs_tolerance2 = 1e-5f;
     p->rel_tolerance2 = 2.5e-4f;
-}
-
-// One launch (rt_adaptive.hip).  Of the context only the device is used.
-rt_status rt_adaptive_error(rt_ctx* ctx, const float* image, const float* moments, float* error,
-                            uint32_t w, uint32_t h, uint32_t min_history, void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
-    if (!image || !moments || !error)
-        return fail(RT_ERR_INVALID_ARGUMENT, "NULL image, moments or error");
-    if (error == image || error == moments)
-        return fail(RT_ERR_INVALID_ARGUMENT, "error is image or moments");
-    if (min_history < 1u || min_history > (1u << 24))
-        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
-    if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    rtk::AdaptiveErrorParams p;
-    p.image = reinterpret_cast<const float4*>(image);
-    p.moments = reinterpret_cast<const float4*>(moments);
-    p.error = error;
-    p.width = w;
-    p.height = h;
-    p.min_history = (float)min_history;
-    hipError_t e = rtk::launch_adaptive_error(p, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "rt_adaptive_error_kernel launch");
-    return RT_OK;
 }
 
 rt_status rt_update_adaptive_bands(rt_ctx* ctx, const float* in, float* out, const float* error,

@@ -1,5 +1,5 @@
 // rt_adaptive_kernels.h — launch interface of rt_adaptive_error's kernel (rt_adaptive.hip) for
-// rt_abi.cpp.  Internal; the public boundary is include/rt_adaptive.h.  (The sampler's kernel
+// rt_post.cpp.  Internal; the public boundary is include/rt_adaptive.h.  (The sampler's kernel
 // lives in rt_kernels.hip beside the tracer it reuses: rt_kernels.h, launch_adaptive.)
 #pragma once
 

@@ -1,19 +1,14 @@
 // rt_denoise_kernels.h — launch interface of the denoiser's kernels (rt_denoise.hip) for
-// rt_abi.cpp.  Internal; the public boundary is include/rt_denoise.h.
+// rt_post.cpp.  Internal; the public boundary is include/rt_denoise.h.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 
-namespace rtk {
+#include "rt_atrous_route.h"
 
-// How one iteration reaches its 25 taps (rt_denoise.hip).
-enum DenoiseRoute : uint32_t {
-    kDenoiseRows = 0,    // LDS: 64 x 4 pixels of one (y mod step) class of rows with a halo of
-                         // 2 * step along x (step <= kDenoiseRowsMaxStep)
-    kDenoiseDirect = 1,  // no LDS: every tap is a global load, one wave per 64-pixel row piece
-};
+namespace rtk {
 
 struct DenoiseParams {
     const float4* in;      // this iteration's input image
@@ -27,8 +22,6 @@ struct DenoiseParams {
     float ic, ip;          // this iteration's 1 / sigma_c^2 (clamped to FLT_MAX), 1 / sigma_p^2
 };
 
-// kDenoiseRows with a step above this is hipErrorInvalidValue.
-constexpr uint32_t kDenoiseRowsMaxStep = 16;
-hipError_t launch_denoise(const DenoiseParams& p, DenoiseRoute route, hipStream_t stream);
+hipError_t launch_denoise(const DenoiseParams& p, AtrousRoute route, hipStream_t stream);
 
 }  // namespace rtk

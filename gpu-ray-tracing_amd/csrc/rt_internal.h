@@ -1,9 +1,11 @@
 // rt_internal.h — helpers shared by the C-ABI translation units of librt_hip.so
-// (rt_abi.cpp, rt_comm.cpp, rt_chain.cpp).  Internal; not part of the public boundary.
+// (rt_abi.cpp, rt_post.cpp, rt_comm.cpp, rt_chain.cpp).  Internal; not part of the public
+// boundary.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
+#include <cfloat>
 #include <string>
 
 #include "rt_abi.h"
@@ -15,8 +17,13 @@ rt_status fail(rt_status s, const std::string& msg);
 rt_status hip_fail(hipError_t e, const char* what);
 // RT_ERR_INVALID_SIZE unless 1 <= w, h <= 65536.
 rt_status check_image(uint32_t w, uint32_t h);
+// Whether a parameter is neither negative, NaN nor infinite.
+inline bool nonneg_finite(float x) { return x >= 0.0f && x <= FLT_MAX; }
 // The HIP device of a context (rt_create's argument).
 int ctx_device(const rt_ctx* ctx);
+// Drops what the context knows about `image`'s sample counts (the source of the kernels' count
+// hint): for a call that leaves per-pixel counts in it.
+void forget_count(rt_ctx* ctx, const void* image);
 // Whether nranks band sets cover every band of a height-row image exactly once, each within
 // rows_per_rank rows (rt_deinterleave_bands' precondition).
 bool band_sets_cover(uint32_t height, uint32_t nranks, const rt_band_set* sets,

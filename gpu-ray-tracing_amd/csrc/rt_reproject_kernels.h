@@ -1,5 +1,5 @@
 // rt_reproject_kernels.h — launch interface of the reprojection kernel (rt_reproject.hip) for
-// rt_abi.cpp.  Internal; the public boundary is include/rt_reproject.h.
+// rt_post.cpp.  Internal; the public boundary is include/rt_reproject.h.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

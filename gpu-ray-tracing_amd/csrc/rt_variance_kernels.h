@@ -1,10 +1,12 @@
 // rt_variance_kernels.h — launch interface of the moments and variance-guided filter kernels
-// (rt_variance.hip) for rt_abi.cpp.  Internal; the public boundary is include/rt_variance.h.
+// (rt_variance.hip) for rt_post.cpp.  Internal; the public boundary is include/rt_variance.h.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+
+#include "rt_atrous_route.h"
 
 namespace rtk {
 
@@ -16,13 +18,6 @@ struct MomentsParams {
 };
 
 hipError_t launch_moments_update(const MomentsParams& p, hipStream_t stream);
-
-// How one iteration reaches its taps (rt_variance.hip): rt_denoise.hip's two
-// routes.
-enum VarianceRoute : uint32_t {
-    kVarianceRows = 0,    // LDS, step <= kVarianceRowsMaxStep
-    kVarianceDirect = 1,  // every tap is a global load
-};
 
 struct VarianceParams {
     const float4* in;       // this iteration's input image
@@ -41,9 +36,6 @@ struct VarianceParams {
     float fallback;         // fallback_variance
 };
 
-// kVarianceRows with a step above this is hipErrorInvalidValue.
-constexpr uint32_t kVarianceRowsMaxStep = 16;
-hipError_t launch_variance_filter(const VarianceParams& p, VarianceRoute route,
-                                  hipStream_t stream);
+hipError_t launch_variance_filter(const VarianceParams& p, AtrousRoute route, hipStream_t stream);
 
 }  // namespace rtk

@@ -120,8 +120,8 @@ def moved_expected(name, what, var):
 
 # ---- launch geometry -------------------------------------------------------------------------------
 def rows_grid(w, h, s):
-    """The rows route's grid as launch_rows computes it, and per block of its y axis the class,
-    the tile and whether the workgroup leaves at once (y0 >= h)."""
+    """The rows route's grid as atrous::launch (csrc/rt_atrous.h) computes it, and per block of
+    its y axis the class, the tile and whether the workgroup leaves at once (y0 >= h)."""
     gx = (w + TILE_W - 1) // TILE_W
     gy = s * (((h + s - 1) // s + TILE_ROWS - 1) // TILE_ROWS)
     blocks = []
