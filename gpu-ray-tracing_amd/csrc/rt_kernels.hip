@@ -145,6 +145,9 @@ __device__ __forceinline__ uint64_t mask_ne(uint32_t a, uint32_t b) {
 __device__ __forceinline__ uint64_t mask_sge(int a, int b) {
     return __builtin_amdgcn_sicmp(a, b, 39);          // ICMP_SGE
 }
+__device__ __forceinline__ uint64_t mask_sgt(int a, int b) {
+    return __builtin_amdgcn_sicmp(a, b, 38);          // ICMP_SGT
+}
 __device__ __forceinline__ uint64_t mask_not_lt(float a, float b) {
     return __builtin_amdgcn_fcmpf(a, b, 11);          // FCMP_UGE: !(a < b)
 }
@@ -1623,6 +1626,43 @@ __device__ __forceinline__ v3 sky_w(v3 cf, v3 d) { return sky_w(cf, d, dot(d, d)
 // ncand[s] its count (kCandNone: the full list; 0 for a tile past the image edge).
 template <uint32_t S>
 constexpr bool kSingleLds = RT_SINGLE_LDS == 2 || (RT_SINGLE_LDS == 1 && S == 1);
+// single_sample's parameters for one frame of a frame group (rt_tpair_kernel)
+struct FrameView {
+    const float4* geom;
+    const float4* sph;
+    uint32_t count, depth, seed_b, normal_rn;
+    float4 rs;
+};
+// A wave-uniform flag word where single_sample tests it.  In a frame loop the word is a loop
+// invariant and so is its test: the compiler hoists the comparison and keeps the i1 as a
+// 64-bit lane mask across the loop (in rt_tpair_kernel spilled to VGPR lanes: two v_readlane
+// a frame per flag, and for normal_rn a v_cndmask + v_cmp_ne to turn the mask back into a
+// branch condition).  Made opaque here, the word is tested where it is used, by s_cmp.  The
+// one-frame kernels have no loop to hoist out of: their flags stay as they are.
+// (kInFrameLoop: single_sample instantiated for a frame loop, i.e. with a FrameView)
+template <typename P>
+constexpr bool kInFrameLoop = false;
+template <>
+constexpr bool kInFrameLoop<FrameView> = true;
+template <typename P>
+__device__ __forceinline__ uint32_t flag_here(const P&, uint32_t x) {
+    if (kInFrameLoop<P>) asm volatile("" : "+s"(x));
+    return x;
+}
+// The list walk's start values (no hit: tmax 3.4e35, index -1) materialised where the walk
+// starts.  As plain constants in a frame loop they are hoisted into four VGPRs that stay
+// live across the loop, and the two tiles' values are copied from them as register pairs
+// (two v_mov_b32 and two v_mov_b64 a frame).
+__device__ __forceinline__ float walk_tmax_here() {
+    float t;
+    asm volatile("v_mov_b32 %0, 0x7a82f697" : "=v"(t));          // 0x1.05ed2ep+118f
+    return t;
+}
+__device__ __forceinline__ int walk_idx_here() {
+    int i;
+    asm volatile("v_mov_b32 %0, -1" : "=v"(i));
+    return i;
+}
 template <uint32_t S, bool kUniRs, typename P>
 __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
                                               const TileCoord (&tc)[S],
@@ -1644,6 +1684,10 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
         get_ray<kSingleDisk>(cam, tc[s].x, tc[s].y, hxy[s], seed[s] * 25u + p.seed_b, o[s],
                              d[s], S > 1 ? &c0 : nullptr);
     }
+    // (the frame loop keeps the shared copy live to here: where it died in the last pixel's
+    // lens FMAs they were written over it, and three v_mov then carried the origin to where
+    // the pinhole branch leaves it)
+    if (S > 1 && kInFrameLoop<P>) asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z));
     SST_V(3, d[S - 1].x);
     const uint32_t lane = threadIdx.x & 63u;
     if (kSingleLds<S>) {
@@ -1662,7 +1706,7 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
         black[s] = false;
         any_other[s] = false;
     }
-    if (p.depth != 0u) {                                          // wgsl:264
+    if (flag_here(p, p.depth) != 0u) {                            // wgsl:264
         // sphere_list_hit over each tile's list, the tiles' chunks interleaved
         float tmax[S], a[S];
         int idx[S];
@@ -1677,6 +1721,13 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
             m = max(m, ncand[s]);
         }
         if (joint) {
+            if (kInFrameLoop<P>) {
+#pragma unroll
+                for (uint32_t s = 0; s < S; ++s) {
+                    tmax[s] = walk_tmax_here();
+                    idx[s] = walk_idx_here();
+                }
+            }
             // (walking the common length jointly and the longer list's rest alone measured
             // neutral: profiles/r06/r06av/)
             for (uint32_t i = 0; i < m; i += K) {
@@ -1732,7 +1783,10 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
         uint64_t hm[S], any_m = 0;
 #pragma unroll
         for (uint32_t s = 0; s < S; ++s) {
-            hm[s] = mask_sge(idx[s], 0) & live_m[s];
+            // idx >= 0; in the frame loop written as the compiler writes the boolean's compare
+            // above (idx > -1): the lane mask and hit[s] then come from one v_cmp instead of
+            // one each (the one-frame kernels' code stays as it was measured)
+            hm[s] = (kInFrameLoop<P> ? mask_sgt(idx[s], -1) : mask_sge(idx[s], 0)) & live_m[s];
             any_m |= hm[s];
         }
         if (any_m != 0ull) {
@@ -1770,7 +1824,7 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
                 bool blk_s, other_s;
                 float ndd;
                 shade_hit(pr[s], mat[s], tmax[s], o[s], d[s], r_sb, ruv, hit[s], hm[s],
-                          p.normal_rn != 0u, nd, att, blk_s, other_s, ndd);
+                          flag_here(p, p.normal_rn) != 0u, nd, att, blk_s, other_s, ndd);
                 any_other[s] = other_s;
                 if (hm[s] == live_m[s]) {
                     // every live lane hit (a tile inside a sphere's image): no selects
@@ -2101,13 +2155,6 @@ __global__ __launch_bounds__(64) void rt_chain_done_kernel(uint32_t* done, uint3
 #ifndef RT_TPAIR_MIN_WAVES
 #define RT_TPAIR_MIN_WAVES 7
 #endif
-// single_sample's parameters for one frame of a frame group
-struct FrameView {
-    const float4* geom;
-    const float4* sph;
-    uint32_t count, depth, seed_b, normal_rn;
-    float4 rs;
-};
 // (G an int: rocprofv3 lists the instances as rt_tpair_kernel<2> / <4>, rt_kernel_name's names)
 template <int G>
 __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
@@ -2176,6 +2223,11 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
                 s_acc[s * 64u + lane] = p.reset_first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f)
                                                       : acc[s];
         const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        // both counts as signed bytes (a count is at most kCandMax, kCandNone is -1) and, from
+        // bit 16, tile[1] - tile[0]: 1, or 0 where the partner tile is outside the image
+        static_assert(kCandMax < 0x80u && kCandNone == 0xFFFFFFFFu, "a count fits a signed byte");
+        const uint32_t unit_state =
+            (ncand[0] & 0xFFu) | (ncand[1] & 0xFFu) << 8 | (tile[1] - tile[0]) << 16;
         for (uint32_t f = 0; f < p.frames; f += Gu) {
             const uint32_t fw = f + w;
             // (single_sample writes every lane's colour; zeros only where nothing is traced)
@@ -2192,8 +2244,8 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
                     v.count = p.count;
                     v.depth = p.depth;
                     v.seed_b = p.seed_b[fw];
-                    // (read from the kernarg segment every frame: as a loop invariant the
-                    // flag was spilled and turned back into a lane mask per pixel, four VALU)
+                    // (depth and normal_rn as words: single_sample tests them where it uses
+                    // them, flag_here)
                     v.normal_rn = p.normal_rn;
                     v.rs = p.hint_rs[fw * p.depth];
                     uint32_t seed[S];
@@ -2208,15 +2260,21 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
                     // (SALU) instead of staying live across the loop: 45 -> 28 SGPRs spilled
                     // to VGPR lanes, 30 -> 14 v_readlane in the loop; K3 13.60 -> 13.37 us per
                     // frame (tools/chain_ab.py, profiles/r06/r06ae/); re-reading the unit and
-                    // the counts through the scalar cache every frame instead: 14.17 (r06af/)
+                    // the counts through the scalar cache every frame instead: 14.17 (r06af/).
+                    // What stays live across the loop is two words, tile[0] and unit_state
+                    // (both counts as signed bytes and the partner bit): tile[1], the
+                    // pointers and the counts are SALU per frame (s_bfe_i32 sign-extends
+                    // the kCandNone byte back to kCandNone); 6 -> 2 v_readlane a frame, 23
+                    // SGPRs spilled (profiles/chain_trim/)
                     const float4* blkf[S];
                     uint32_t ncf[S];
+                    uint32_t t0 = tile[0], st = unit_state;
+                    asm volatile("" : "+s"(t0), "+s"(st));
 #pragma unroll
                     for (uint32_t s = 0; s < S; ++s) {
-                        uint32_t t = tile[s], nc = ncand[s];
-                        asm volatile("" : "+s"(t), "+s"(nc));
+                        const uint32_t t = t0 + (s ? st >> 16 : 0u);
                         blkf[s] = a_cand + (size_t)t * kCandStride;
-                        ncf[s] = nc;
+                        ncf[s] = (uint32_t)((int32_t)(st << (24u - 8u * s)) >> 24);
                     }
                     single_sample<S, true>(v, cam, tc, hxy, seed, blkf, ncf, live, valid_m, bv,
                                            nullptr, col);
