@@ -22,6 +22,7 @@
 #include "rt_chain_parts.h"
 #include "rt_selftest_roots.h"
 #include "rt_adaptive.h"
+#include "rt_converge.h"
 #include "rt_device.h"
 #ifdef RT_CALL_STAMPS
 // (diagnostic builds: host time stamps of rt_update_frames' phases, one stderr line per call)
@@ -1733,6 +1734,24 @@ rt_status rt_pick(rt_ctx* ctx, uint32_t w, uint32_t h, uint32_t x, uint32_t y,
 
 namespace {
 
+// What rt_update_adaptive and rt_converge_frames refuse of an rt_adaptive_params.
+rt_status check_adaptive_params(const rt_adaptive_params& params) {
+    if (params.min_samples > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
+    if (!rti::nonneg_finite(params.abs_tolerance2) || !rti::nonneg_finite(params.rel_tolerance2))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
+    return RT_OK;
+}
+
+// The instance of rt_adaptive_kernel / rt_converge_kernel for a prepared launch: the context's
+// as trace_kernel_for chooses it, with ray_color's culled scans in place of the bounce instance
+// at max_depth >= 2.  The culled scans read the records from L2: no LDS copy.
+int adaptive_kernel_for(const rt_ctx* ctx, rtk::TraceParams& p) {
+    p.lds_records = 0u;
+    const int auto_kernel = trace_kernel_for(ctx, p);
+    return auto_kernel == rtk::kTraceBounce ? rtk::kTraceCulled : auto_kernel;
+}
+
 // Shared body of rt_update_adaptive / rt_update_adaptive_bands (rt_adaptive.h): the argument
 // checks, then prepare() as every trace launch (scene upload, hash tables, candidate lists) and
 // one rt_adaptive_kernel launch over the band set.  The instance follows the context as
@@ -1747,11 +1766,7 @@ rt_status update_adaptive(rt_ctx* ctx, const float* in, float* out, const float*
     if (out == in || static_cast<const void*>(out) == error ||
         static_cast<const void*>(out) == tile_mask)
         return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is in_rgba, error or tile_mask");
-    if (params->min_samples > (1u << 24))
-        return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
-    const float at2 = params->abs_tolerance2, rt2 = params->rel_tolerance2;
-    if (!rti::nonneg_finite(at2) || !rti::nonneg_finite(rt2))
-        return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
+    if (rt_status s = check_adaptive_params(*params)) return s;
     if (rt_status s = check_image(w, h)) return s;
     if (rt_status s = check_band_set(h, bs)) return s;
     DeviceGuard guard(ctx->device);
@@ -1767,18 +1782,77 @@ rt_status update_adaptive(rt_ctx* ctx, const float* in, float* out, const float*
     p.frames = 1u;
     p.reset_first = cam->camera_has_moved > 0.5f ? 1u : 0u;
     p.seed_b[0] = host_f2u(seed * 4294967296.0f);
-    p.lds_records = 0u;              // (the culled scans read the records from L2)
-    const int auto_kernel = trace_kernel_for(ctx, p);
-    const int kernel = auto_kernel == rtk::kTraceBounce ? rtk::kTraceCulled : auto_kernel;
+    const int kernel = adaptive_kernel_for(ctx, p);
     rtk::AdaptiveParams a;
     a.error = error;
     a.tile_mask = tile_mask;
     a.min_samples = params->min_samples;
-    a.abs_tolerance2 = at2;
-    a.rel_tolerance2 = rt2;
+    a.abs_tolerance2 = params->abs_tolerance2;
+    a.rel_tolerance2 = params->rel_tolerance2;
     forget_count(ctx, out);          // the counts now differ per pixel
     hipError_t e = rtk::launch_adaptive(p, a, kernel, stream);
     if (e != hipSuccess) return hip_fail(e, "rt_adaptive_kernel launch");
+    return RT_OK;
+}
+
+// Shared body of rt_converge_frames / rt_converge_frames_bands (rt_converge.h): the argument
+// checks, prepare() as update_adaptive, then one rt_converge_kernel launch per
+// RT_CONVERGE_MAX_FRAMES_PER_LAUNCH frames, in order on the caller's stream, with the seeds
+// converted as rt_update_frames converts them.  The same instance choice, and like
+// update_adaptive no hint, no tile order, no cost recording, no launch info.
+static_assert(rtk::kConvergeMaxFrames == RT_CONVERGE_MAX_FRAMES_PER_LAUNCH,
+              "the kernel's frames per launch are the header's");
+rt_status converge_frames(rt_ctx* ctx, float* image, float* moments, float* error,
+                          uint64_t* tile_mask, uint32_t* tile_samples, uint32_t w, uint32_t h,
+                          const rt_band_set& bs, const rt_scene_camera* cam,
+                          const rt_sphere* spheres, uint32_t count, uint32_t frames,
+                          const float* seeds, const rt_adaptive_params* params,
+                          uint32_t min_history, void* stream_v) {
+    if (!image || !moments || !cam || !params || !seeds)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "NULL image, moments, camera, params or random_seeds");
+    const void* const bufs[5] = {image, moments, error, tile_mask, tile_samples};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (bufs[i] && bufs[i] == bufs[j])
+                return fail(RT_ERR_INVALID_ARGUMENT,
+                            "two of image, moments, error, tile_mask and tile_samples are equal");
+    if (frames == 0u || frames > 65536u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "frames outside 1..65536");
+    if (min_history == 0u || min_history > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
+    if (rt_status s = check_adaptive_params(*params)) return s;
+    if (rt_status s = check_image(w, h)) return s;
+    if (rt_status s = check_band_set(h, bs)) return s;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    rtk::TraceParams p;
+    if (rt_status s = prepare(ctx, image, image, w, h, bs, cam, spheres, count, seeds, stream, p))
+        return s;
+    if (bs.count == 0) return RT_OK;
+    p.in = reinterpret_cast<const float4*>(image);
+    p.out = reinterpret_cast<float4*>(image);
+    const int kernel = adaptive_kernel_for(ctx, p);
+    rtk::ConvergeParams a;
+    a.moments = reinterpret_cast<float4*>(moments);
+    a.error = error;
+    a.tile_mask = tile_mask;
+    a.tile_samples = tile_samples;
+    a.min_samples = params->min_samples;
+    a.abs_tolerance2 = params->abs_tolerance2;
+    a.rel_tolerance2 = params->rel_tolerance2;
+    a.min_history = (float)min_history;
+    forget_count(ctx, image);        // the counts now differ per pixel
+    for (uint32_t f0 = 0; f0 < frames; f0 += rtk::kConvergeMaxFrames) {
+        const uint32_t nf = std::min(frames - f0, rtk::kConvergeMaxFrames);
+        p.frames = nf;
+        p.reset_first = (f0 == 0u && cam->camera_has_moved > 0.5f) ? 1u : 0u;
+        for (uint32_t f = 0; f < nf; ++f) p.seed_b[f] = host_f2u(seeds[f0 + f] * 4294967296.0f);
+        a.first = f0 == 0u ? 1u : 0u;
+        hipError_t e = rtk::launch_converge(p, a, kernel, stream);
+        if (e != hipSuccess) return hip_fail(e, "rt_converge_kernel launch");
+    }
     return RT_OK;
 }
 
@@ -1812,6 +1886,31 @@ rt_status rt_update_adaptive(rt_ctx* ctx, const float* in, float* out, const flo
     const rt_band_set all = stripe_set(h, 0, 1);    // (h is checked below, before the set is)
     return update_adaptive(ctx, in, out, error, tile_mask, w, h, all, cam, spheres, count, params,
                            stream);
+}
+
+rt_status rt_converge_frames_bands(rt_ctx* ctx, float* image, float* moments, float* error,
+                                   uint64_t* tile_mask, uint32_t* tile_samples, uint32_t w,
+                                   uint32_t h, const rt_band_set* bands,
+                                   const rt_scene_camera* cam, const rt_sphere* spheres,
+                                   uint32_t count, uint32_t frames, const float* seeds,
+                                   const rt_adaptive_params* params, uint32_t min_history,
+                                   void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!bands) return fail(RT_ERR_INVALID_ARGUMENT, "bands is NULL");
+    return converge_frames(ctx, image, moments, error, tile_mask, tile_samples, w, h, *bands, cam,
+                           spheres, count, frames, seeds, params, min_history, stream);
+}
+
+rt_status rt_converge_frames(rt_ctx* ctx, float* image, float* moments, float* error,
+                             uint64_t* tile_mask, uint32_t* tile_samples, uint32_t w, uint32_t h,
+                             const rt_scene_camera* cam, const rt_sphere* spheres,
+                             uint32_t count, uint32_t frames, const float* seeds,
+                             const rt_adaptive_params* params, uint32_t min_history,
+                             void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    const rt_band_set all = stripe_set(h, 0, 1);    // (h is checked below, before the set is)
+    return converge_frames(ctx, image, moments, error, tile_mask, tile_samples, w, h, all, cam,
+                           spheres, count, frames, seeds, params, min_history, stream);
 }
 
 }  // extern "C"

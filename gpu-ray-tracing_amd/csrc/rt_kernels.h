@@ -307,6 +307,24 @@ struct AdaptiveParams {
 // kTraceList or kTraceCulled
 hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int kernel,
                            hipStream_t stream);
+// Fused adaptive rounds (rt_converge.h; rt_kernels.hip rt_converge_kernel): p.frames rounds of
+// error, adaptive update and moments update over p's stripes, the image in place (p.out).
+constexpr uint32_t kConvergeMaxFrames = 64;   // RT_CONVERGE_MAX_FRAMES_PER_LAUNCH
+static_assert(kConvergeMaxFrames <= kMaxFramesPerLaunch, "the launch's seeds fit seed_b");
+struct ConvergeParams {
+    float4* moments;           // the local moments image, read and rewritten in place
+    float* error;              // per pixel: the final error (null: not wanted)
+    uint64_t* tile_mask;       // per local tile: the lanes the last frame sampled (null: not wanted)
+    uint32_t* tile_samples;    // per local tile: the samples taken (null: not wanted)
+    uint32_t first;            // 1: the call's first launch (tile_samples is written, not added to)
+    uint32_t min_samples;
+    float abs_tolerance2, rel_tolerance2;
+    float min_history;         // (float)min_history
+};
+// p: frames 1..kConvergeMaxFrames with their seed_b, out = the image, no hint, lds_records 0;
+// kernel: as launch_adaptive
+hipError_t launch_converge(const TraceParams& p, const ConvergeParams& a, int kernel,
+                           hipStream_t stream);
 const char* trace_kernel_name();
 // "rt_single_kernel<p>": p = pix tiles per wave (0: kTraceSingle's)
 const char* single_kernel_name(uint32_t pix);

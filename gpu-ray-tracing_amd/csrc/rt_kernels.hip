@@ -4174,6 +4174,169 @@ hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int ke
     return hipGetLastError();
 }
 
+// ---- Fused adaptive rounds (rt_converge.h) ---------------------------------------------
+//
+// p.frames rounds of rt_adaptive_error, rt_update_adaptive and rt_moments_update over one tile
+// in one launch, beside rt_adaptive_kernel for that kernel's reason (sample<kScan> and
+// ray_color as they are) and on its grid: one wave per 8x8 tile, four tiles of a band per
+// workgroup.  The wave loads its accumulator and moments texels once, keeps both in registers
+// over the frames and stores them once, in place (p.out; nothing reads a tile's texels during
+// the launch but its own wave).  Each frame, in f32 and in the headers' order of operations:
+// the error from the moments and the count (rt_adaptive.h), the decision and its ballot, one
+// sample with the ballot's lanes live when it is not empty (seed_b[f]; no hint), the IEEE
+// division of wgsl:356, and rt_variance.h's four rules on the texel before and after the frame.
+// Control flow is wave-uniform (ballots); the per-lane rules are selects.
+//
+// Early exit: a frame that is not a reset, in which no lane was sampled and
+// which left every on-image lane's accumulator and moments texels bit-identical to what it
+// read, is a fixed point: every later frame reads the same state, decides the same (only the
+// seed differs, and no idle lane reads it) and writes the same.  The wave leaves the loop
+// there.  "No lane sampled" alone would not do: a count of 7.5 passes through as 7, rule 4 then
+// zeroes the moments, the error becomes +inf and the pixel is sampled in the next frame.
+// A wave none of whose frames changed a bit stores no texel.
+// The culled instance holds eight more live registers than rt_adaptive_kernel's across ray_color's
+// culled scans: planned for RT_TRACE_MIN_WAVES it spills to scratch (44 bytes per lane), so it is
+// planned for 6 waves per SIMD (74 VGPRs, no scratch); the other two fit as they are.
+template <int kScan>
+constexpr int converge_min_waves() {
+    return kScan == kTraceCulled ? 6 : RT_TRACE_MIN_WAVES;
+}
+template <int kScan>
+__global__ __launch_bounds__(256, converge_min_waves<kScan>()) void rt_converge_kernel(
+    const TraceParams p, const ConvergeParams a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t tiles_x = (p.width + 7u) >> 3;
+    const uint32_t tx = blockIdx.x * 4u + wave;
+    if (tx >= tiles_x) return;                                    // whole wave exits
+    const uint32_t lband = blockIdx.y;
+    const TileCoord tc = tile_coord(p, tx, lband, lane);
+    const uint32_t tile = lband * tiles_x + tx;
+    // (a lane off the image holds zeros, is never sampled and stores nothing)
+    float4 I = make_float4(0.0f, 0.0f, 0.0f, 0.0f), M = I;
+    if (tc.valid) {
+        I = p.out[tc.idx];
+        M = a.moments[tc.idx];
+    }
+    const uint32_t spp = p.spp;                                   // wgsl:343
+    uint32_t ncand = kCandNone, hxy = 0u;
+    bool scene_read = false;                // the tile's list and seed hashes: on first use
+    bool dirty = false;                     // some frame changed a bit of the tile
+    uint64_t m = 0ull;
+    uint32_t taken = 0u;
+    for (uint32_t f = 0; f < p.frames; ++f) {
+        const bool reset = f == 0u && p.reset_first != 0u;
+        // rt_adaptive_error
+        float d = M.y - M.x * M.x;
+        d = d > 0.0f ? d : 0.0f;
+        const float nn = I.w > 1.0f ? I.w : 1.0f;
+        const float err = M.w >= a.min_history ? d / nn : __builtin_inff();
+        // rt_update_adaptive
+        v3 c = mk(0.0f, 0.0f, 0.0f);
+        uint32_t n = 0u;
+        bool sampled = 0u < spp;                                  // a reset: wgsl:345-350
+        if (!reset) {
+            c = mk(I.x, I.y, I.z);                                // wgsl:339-341
+            n = f2u(I.w);
+            const float lm = (0.2126f * I.x + 0.7152f * I.y) + 0.0722f * I.z;
+            const float thr = a.abs_tolerance2 + a.rel_tolerance2 * (lm * lm);
+            const bool converged = n >= a.min_samples && err <= thr;  // (a NaN: not converged)
+            sampled = n < spp && !converged;
+        }
+        sampled = sampled && tc.valid;
+        m = rt_ballot(sampled);
+        if (m != 0ull) {
+            if (!scene_read) {
+                ncand = (kScan != kTraceExhaustive && p.cand) ? load_cnt(p.cand, tile)
+                                                              : kCandNone;
+                hxy = p.hx[min(tc.x, p.width - 1u)] ^ p.hy[min(tc.y, p.height - 1u)];
+                scene_read = true;
+            }
+            const Cam cam = cam_params(p);
+            const v3 col = sample<kScan>(p, cam, tile, ncand, tc, hxy, n, p.seed_b[f], f, sampled,
+                                         false);
+            if (sampled) {
+                const float k = (float)(n + 1u);                  // wgsl:356
+                c = mk(c.x + (col.x - c.x) / k, c.y + (col.y - c.y) / k, c.z + (col.z - c.z) / k);
+                n += 1u;
+            }
+            taken += (uint32_t)__popcll(m);
+        }
+        const float4 O = make_float4(c.x, c.y, c.z, (float)n);    // wgsl:362-363
+        // rt_moments_update on (I, O): rules 1 and 2 share the running means' step, rule 3 keeps
+        // M and rule 4 zeroes it
+        const bool r1 = O.w == 1.0f;
+        const bool r2 = !r1 && O.w == I.w + 1.0f;
+        float4 N = M;
+        if (!(r1 || r2) && !(O.w == I.w)) N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (rt_ballot(r1 || r2) != 0ull) {
+            const float sx = r1 ? O.x : I.x + O.w * (O.x - I.x);
+            const float sy = r1 ? O.y : I.y + O.w * (O.y - I.y);
+            const float sz = r1 ? O.z : I.z + O.w * (O.z - I.z);
+            const float k0 = r1 ? 0.0f : M.w;
+            const bool fresh = k0 == 0.0f;
+            const float m1 = fresh ? 0.0f : M.x, m2 = fresh ? 0.0f : M.y;
+            const float L = (0.2126f * sx + 0.7152f * sy) + 0.0722f * sz;
+            const float kk = k0 + 1.0f;
+            const float4 S = make_float4(m1 + (L - m1) / kk, m2 + (L * L - m2) / kk, 0.0f, kk);
+            if (r1 || r2) N = S;
+        }
+        const bool changed =
+            tc.valid &&
+            (((__float_as_uint(O.x) ^ __float_as_uint(I.x)) |
+              (__float_as_uint(O.y) ^ __float_as_uint(I.y)) |
+              (__float_as_uint(O.z) ^ __float_as_uint(I.z)) |
+              (__float_as_uint(O.w) ^ __float_as_uint(I.w)) |
+              (__float_as_uint(N.x) ^ __float_as_uint(M.x)) |
+              (__float_as_uint(N.y) ^ __float_as_uint(M.y)) |
+              (__float_as_uint(N.z) ^ __float_as_uint(M.z)) |
+              (__float_as_uint(N.w) ^ __float_as_uint(M.w))) != 0u);
+        const bool any_changed = rt_ballot(changed) != 0ull;
+        I = O;
+        M = N;
+        dirty = dirty || any_changed;
+        if (!any_changed && m == 0ull && !reset) break;           // a fixed point: see above
+    }
+    // (after an early exit m is 0: the frames left out sample nothing)
+    if (lane == 0u) {
+        if (a.tile_mask) a.tile_mask[tile] = m;
+        if (a.tile_samples) {
+            if (a.first)
+                a.tile_samples[tile] = taken;
+            else if (taken != 0u)
+                a.tile_samples[tile] += taken;
+        }
+    }
+    // a later launch of the call that changes nothing finds the plane its predecessor wrote
+    if (!tc.valid || !(dirty || a.first)) return;
+    if (dirty) {
+        p.out[tc.idx] = I;
+        a.moments[tc.idx] = M;
+    }
+    if (a.error) {
+        float d = M.y - M.x * M.x;
+        d = d > 0.0f ? d : 0.0f;
+        const float nn = I.w > 1.0f ? I.w : 1.0f;
+        a.error[tc.idx] = M.w >= a.min_history ? d / nn : __builtin_inff();
+    }
+}
+
+hipError_t launch_converge(const TraceParams& p, const ConvergeParams& a, int kernel,
+                           hipStream_t stream) {
+    const dim3 grid = tile_grid(p);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    if (kernel == kTraceList)
+        hipLaunchKernelGGL(rt_converge_kernel<kTraceList>, grid, dim3(256), 0, stream, p, a);
+    else if (kernel == kTraceCulled)
+        hipLaunchKernelGGL(rt_converge_kernel<kTraceCulled>, grid, dim3(256), 0, stream, p, a);
+    else if (kernel == kTraceExhaustive)
+        hipLaunchKernelGGL(rt_converge_kernel<kTraceExhaustive>, grid, dim3(256), 0, stream, p,
+                           a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 const char* trace_kernel_name() { return "rt_trace_kernel"; }
 const char* single_kernel_name(uint32_t pix) {
     static const char* const names[] = {"rt_single_kernel<1>", "rt_single_kernel<2>",

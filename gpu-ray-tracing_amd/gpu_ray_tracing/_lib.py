@@ -244,6 +244,16 @@ class AdaptiveParamsC(ctypes.Structure):
     _fields_ = [("min_samples", U32), ("abs_tolerance2", F), ("rel_tolerance2", F)]
 
 
+# include/rt_converge.h (the adaptive round as one multi-frame launch)
+_SIGS_CONVERGE = {
+    "rt_converge_frames": (ctypes.c_int, [P, P, P, P, P, P, U32, U32, P, P, U32, U32, P, P, U32,
+                                          P]),
+    "rt_converge_frames_bands": (ctypes.c_int, [P, P, P, P, P, P, U32, U32, P, P, P, U32, U32, P,
+                                                P, U32, P]),
+}
+RT_CONVERGE_MAX_FRAMES_PER_LAUNCH = 64
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -289,7 +299,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
-                                  **_SIGS_VARIANCE, **_SIGS_ADAPTIVE}.items():
+                                  **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -356,6 +366,10 @@ def variance_symbols() -> list[str]:
 
 def adaptive_symbols() -> list[str]:
     return list(_SIGS_ADAPTIVE)
+
+
+def converge_symbols() -> list[str]:
+    return list(_SIGS_CONVERGE)
 
 
 def check(status: int, func: str) -> None:

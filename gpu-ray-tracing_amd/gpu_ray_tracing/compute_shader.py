@@ -799,6 +799,55 @@ class ComputeShaderPipeline:
             _lib.call("rt_update_adaptive_bands", *head, _lib.band_sets([bands]), *tail)
         return mask
 
+    # ---- the adaptive round as one multi-frame launch (rt_converge.h) --------------------
+    def converge(self, image: torch.Tensor, moments: torch.Tensor, width: int, height: int,
+                 camera: SceneCamera, spheres: SphereCollection, seeds, *,
+                 min_samples: int = ADAPTIVE_DEFAULTS["min_samples"],
+                 abs_tolerance2: float = ADAPTIVE_DEFAULTS["abs_tolerance2"],
+                 rel_tolerance2: float = ADAPTIVE_DEFAULTS["rel_tolerance2"],
+                 min_history: int = 4, error=None, tile_mask=False, tile_samples=False,
+                 bands=None):
+        """rt_converge_frames / rt_converge_frames_bands: len(seeds) rounds of adaptive_error,
+        update_adaptive and moments_update on `image` and `moments`, both rewritten in place,
+        bit for bit what the three calls leave; frame 0 honours camera.camera_has_moved.
+        Returns (error, tile_mask, tile_samples), None for each one not wanted: `error` (True:
+        allocated, or a float32 tensor of width * rows elements) receives adaptive_error of the
+        result, `tile_mask` (True, or an int64 tensor of one word per 8 x 8 tile) the pixels the
+        last frame sampled in update_adaptive's layout, `tile_samples` (True, or an int32 tensor
+        of one word per tile) the samples each tile took over the call.  bands = (first, step,
+        count): compact local buffers, as update_adaptive.  Enqueued on torch's current
+        stream."""
+        rows = height if bands is None else int(bands[2]) * RT_STRIPE_ROWS
+        _check_image(image, width, rows, "image")
+        _check_image(moments, width, rows, "moments")
+        tiles = ((width + 7) // 8) * ((rows + 7) // 8)
+
+        def optional(t, shape, dtype, name):
+            if t is None or t is False:
+                return None
+            if t is True:
+                return torch.empty(shape, dtype=dtype, device=self.torch_device)
+            return _check_plane(t, int(np.prod(shape)), dtype, name)
+
+        err = optional(error, (rows, width), torch.float32, "error")
+        mask = optional(tile_mask, (tiles,), torch.int64, "tile_mask")
+        taken = optional(tile_samples, (tiles,), torch.int32, "tile_samples")
+        s = np.ascontiguousarray(seeds, np.float32)
+        params = _lib.AdaptiveParamsC(int(min_samples), float(abs_tolerance2),
+                                      float(rel_tolerance2))
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        head = (self._ctx, _ptr(image), _ptr(moments), *(_ptr(t) if t is not None else None
+                                                         for t in (err, mask, taken)),
+                width, height)
+        tail = (ctypes.byref(cam), p, n, s.size, _np_ptr(s), ctypes.byref(params),
+                int(min_history), self._stream())
+        if bands is None:
+            _lib.call("rt_converge_frames", *head, *tail)
+        else:
+            _lib.call("rt_converge_frames_bands", *head, _lib.band_sets([bands]), *tail)
+        return err, mask, taken
+
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:
         """8-bit RGBA of a float image (rt_present_rgba8), a (H, W, 4) uint8 device tensor:
