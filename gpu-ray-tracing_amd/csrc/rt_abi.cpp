@@ -215,7 +215,7 @@ double norm3d(const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[
 
 // Whether every camera ray of p's camera, image and stripes, against the context's scene,
 // stays inside the domain where the camera-ray-only instances use the exact fast division
-// and sqrt cores (rt_kernels.hip consider_fast / fast_core): a = |d|^2 in [2^-11, 2^20],
+// and sqrt cores (rt_trace_device.h consider_fast / fast_core): a = |d|^2 in [2^-11, 2^20],
 // |O| + max(|C| + |R|) <= 2^40 (so |h|, sqrt(D) <= 2^53 and the hit-point numerators of
 // the normal <= 2^43), and every |R| in [2^-20, 2^20].  d = pc - O (get_ray,
 // wgsl:305-325) with pc = vul + sx pdu + sy pdv, sx in [0, W + 8], sy in [0, H + 8] (lanes
@@ -297,7 +297,7 @@ uint32_t frames_per_launch_for(const rt_ctx* ctx, const rtk::TraceParams& p) {
     return rtk::kHintFrames;
 }
 
-// Uniform XZ grid of the small spheres (rt_kernels.hip scan_grid), built on every scene
+// Uniform XZ grid of the small spheres (rt_trace_device.h scan_grid), built on every scene
 // upload of at least kGridMinSpheres spheres whose |C| + |R| stay within 2^40 (so no f32
 // intermediate of the root test overflows for the rays that may use the grid).  Small:
 // |R| <= 4x the median radius; the others (the ground, the few large spheres) go to the

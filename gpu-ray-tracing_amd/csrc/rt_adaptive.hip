@@ -1,13 +1,16 @@
 // rt_adaptive.hip — the kernel of rt_adaptive_error (include/rt_adaptive.h has the normative
 // definition; DESIGN.md §4.10 the measurements).  A translation unit of its own, like
-// rt_variance.hip: the render's kernels are not recompiled with it.
+// rt_variance.hip: the render's kernels are not recompiled with it.  (rt_update_adaptive's and
+// rt_converge_frames' kernels trace rays: they are in rt_sampler.hip, over the tracer's device
+// library.)
 //
-// Every float operation below is the one the header names, in its order: the build has
-// -ffp-contract=off, IEEE division and subnormals on, so the output is bit-identical to the
-// NumPy restatement in tests/test_adaptive.py.
+// Every float operation below is the one the header names, in its order (rt_pixel_rules.h): the
+// build has -ffp-contract=off, IEEE division and subnormals on, so the output is bit-identical
+// to the NumPy restatement in tests/test_adaptive.py.
 #include <hip/hip_runtime.h>
 
 #include "rt_adaptive_kernels.h"
+#include "rt_pixel_rules.h"
 
 namespace rtk {
 
@@ -19,10 +22,7 @@ __global__ __launch_bounds__(256) void rt_adaptive_error_kernel(const AdaptiveEr
     if (at >= (size_t)p.width * p.height) return;
     const float n = p.image[at].w;
     const float4 m = p.moments[at];
-    float d = m.y - m.x * m.x;
-    d = d > 0.0f ? d : 0.0f;
-    const float nn = n > 1.0f ? n : 1.0f;
-    p.error[at] = m.w >= p.min_history ? d / nn : __builtin_inff();
+    p.error[at] = gated_variance(m.x, m.y, m.w, n, p.min_history, __builtin_inff());
 }
 
 hipError_t launch_adaptive_error(const AdaptiveErrorParams& p, hipStream_t stream) {

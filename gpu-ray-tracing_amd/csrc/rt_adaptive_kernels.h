@@ -1,6 +1,6 @@
 // rt_adaptive_kernels.h — launch interface of rt_adaptive_error's kernel (rt_adaptive.hip) for
-// rt_post.cpp.  Internal; the public boundary is include/rt_adaptive.h.  (The sampler's kernel
-// lives in rt_kernels.hip beside the tracer it reuses: rt_kernels.h, launch_adaptive.)
+// rt_post.cpp.  Internal; the public boundary is include/rt_adaptive.h.  (The sampler's kernels
+// trace rays and live in rt_sampler.hip, over rt_trace_device.h: rt_kernels.h, launch_adaptive.)
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -177,7 +177,7 @@ RT_HD float reflectance(float cos_t, float ri) {
 // for every finite x >= 2^-96 — all 1.88e9 of them are compared on the device by the
 // self-test — and NaN for +0 and +inf, which are outside its domain.
 // Used where the operands are in the domain by construction or by a wave-wide check
-// (rt_kernels.hip: defocus disk, roots, normal, sky, metal / dielectric normalisations);
+// (rt_trace_device.h, rt_kernels.hip: defocus disk, roots, normal, sky, metal / dielectric normalisations);
 // tests/test_gpu_parity.py::test_fastmath_selftest checks both against the IEEE operations
 // on the GPU over that domain; the root selections built on them (consider_fast,
 // consider_any_fast) are compared with consider() / consider_any() over the domain their

@@ -1,5 +1,5 @@
 // rt_kernels.h — launch interface between the C-ABI layer (rt_abi.cpp) and the HIP
-// kernels (rt_kernels.hip).  Internal; not part of the public boundary.
+// kernels (rt_kernels.hip; rt_aov.hip, rt_sampler.hip, rt_selftest.hip).  Internal; not part of the public boundary.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -69,7 +69,7 @@ struct TraceParams {
     // Fused frame-group launches (rt_set_chain_parts): tile_order is a unit order dealt into
     // `parts` sub-lists and the launch runs sub-list `part` (rt_kernels.hip chain_part_grid).
     uint32_t part, parts;
-    // Uniform XZ grid over the small spheres for bounce rays (rt_kernels.hip scan_grid;
+    // Uniform XZ grid over the small spheres for bounce rays (rt_trace_device.h scan_grid;
     // built by rt_abi.cpp build_grid): per cell the range of its items, each item a copy
     // of the sphere's scan record and its index (every small sphere is registered in the
     // cells near its centre); grid_big lists the other spheres.  grid_nx == 0: no grid.
@@ -141,7 +141,7 @@ struct TraceParams {
     uint32_t hint_rs_dev_frames;
     uint32_t hint_n[kHintFrames];
     // RN32(1 / f32(hint_n[f] + 1)): the accumulator's division by f32(n + 1) as a Markstein
-    // division (rtd::div_rn; exact for integer n + 1 < 2^22, rt_kernels.hip kAccRnMax)
+    // division (rtd::div_rn; exact for integer n + 1 < 2^22, rt_trace_device.h kAccRnMax)
     float hint_rcp[kHintFrames];
     // f32 of the count after frame f: f32(hint_n[f] + 1) where the frame accumulates
     // (hint_n[f] < spp: also the divisor k of wgsl:356), else f32(hint_n[f]) — the image's
@@ -275,7 +275,7 @@ hipError_t launch_deinterleave(const float4* gathered, float4* out, uint32_t wid
 // for the linear encoding.
 hipError_t launch_present(const float4* in, uchar4* out, uint64_t texels,
                           const float* srgb_t, hipStream_t stream);
-// First-hit G-buffer (rt_aov.h; rt_kernels.hip rt_aov_kernel): the hit record of each pixel's
+// First-hit G-buffer (rt_aov.h; rt_aov.hip rt_aov_kernel): the hit record of each pixel's
 // centre ray, written out instead of shaded.  Planes not wanted are null (not all of them).
 struct AovParams {
     uint32_t* id;        // per pixel: the winning sphere's index, RT_AOV_MISS for none
@@ -295,7 +295,7 @@ struct AovParams {
 };
 // waves tx0 .. tx0 + tiles_x - 1 of local bands [0, bands): one wave per 8x8 tile
 hipError_t launch_aov(const AovParams& p, uint32_t tiles_x, uint32_t bands, hipStream_t stream);
-// Adaptive sampling (rt_adaptive.h; rt_kernels.hip rt_adaptive_kernel): one update over p's
+// Adaptive sampling (rt_adaptive.h; rt_sampler.hip rt_adaptive_kernel): one update over p's
 // image and stripes in which a pixel takes a sample only while its error is above the tolerance.
 struct AdaptiveParams {
     const float* error;        // per pixel of the local image: the estimated error
@@ -307,7 +307,7 @@ struct AdaptiveParams {
 // kTraceList or kTraceCulled
 hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int kernel,
                            hipStream_t stream);
-// Fused adaptive rounds (rt_converge.h; rt_kernels.hip rt_converge_kernel): p.frames rounds of
+// Fused adaptive rounds (rt_converge.h; rt_sampler.hip rt_converge_kernel): p.frames rounds of
 // error, adaptive update and moments update over p's stripes, the image in place (p.out).
 constexpr uint32_t kConvergeMaxFrames = 64;   // RT_CONVERGE_MAX_FRAMES_PER_LAUNCH
 static_assert(kConvergeMaxFrames <= kMaxFramesPerLaunch, "the launch's seeds fit seed_b");

@@ -56,8 +56,6 @@ __device__ __forceinline__ void wave_trace(int end) {
     }
 }
 #define WAVE_TRACE(e) wave_trace(e)
-#else
-#define WAVE_TRACE(e) ((void)0)
 #endif
 
 // ---- diagnostic bounce counters (RT_BOUNCE_COUNTS=1 builds only; never in the product) ---
@@ -77,8 +75,6 @@ __device__ __forceinline__ void bcount(int k) {
     }
 }
 #define BCOUNT(k) bcount(k)
-#else
-#define BCOUNT(k) ((void)0)
 #endif
 
 // ---- diagnostic phase stamps of the one-frame kernel (RT_SSTAMPS=1 builds only) ------
@@ -115,1080 +111,16 @@ __device__ __forceinline__ void sst_put(int k, unsigned long long t) {
 // (asm-inspection builds: a comment in the code at each phase boundary, after its value)
 #define SST_V(k, dep) asm volatile(";MARK " #k ::"v"(dep))
 #define SST_S(k, dep) asm volatile(";MARK " #k ::"s"(dep))
-#else
-#define SST_V(k, dep) ((void)0)
-#define SST_S(k, dep) ((void)0)
 #endif
 
-// Wave ballot of a per-lane condition.  HIP's __ballot(int) takes the predicate as an int,
-// and the bool -> int -> bool round trip costs a v_cndmask + v_cmp per ballot on gfx950;
-// the builtin takes the condition's lane mask as it is.
-__device__ __forceinline__ unsigned long long rt_ballot(bool x) {
-    return __builtin_amdgcn_ballot_w64(x);
-}
-// The one-frame kernel's (and normalize_w's) wave-uniform decisions come from lane masks
-// (mask_*) instead of ballots: lane masks straight from one compare (llvm.amdgcn.icmp /
-// fcmp: the v_cmp's SGPR result), combined with & and | as 64-bit scalars.  A ballot of a
-// boolean that crosses blocks or combines earlier booleans compiles to a v_cndmask 0/1 +
-// v_cmp_ne round trip (two 4-cycle VALU operations) at every use; these do not (round 3:
-// K3 19.5-19.8 -> 18.9-19.1 µs, K2 13.6-13.8 -> 13.4 µs per update,
-// profiles/r03/r03t_ab_single_masks_all.log).
-__device__ __forceinline__ uint64_t mask_ult(uint32_t a, uint32_t b) {
-    return __builtin_amdgcn_uicmp(a, b, 36);          // ICMP_ULT
-}
-__device__ __forceinline__ uint64_t mask_uge(uint32_t a, uint32_t b) {
-    return __builtin_amdgcn_uicmp(a, b, 35);          // ICMP_UGE
-}
-__device__ __forceinline__ uint64_t mask_ne(uint32_t a, uint32_t b) {
-    return __builtin_amdgcn_uicmp(a, b, 33);          // ICMP_NE
-}
-__device__ __forceinline__ uint64_t mask_sge(int a, int b) {
-    return __builtin_amdgcn_sicmp(a, b, 39);          // ICMP_SGE
-}
-__device__ __forceinline__ uint64_t mask_sgt(int a, int b) {
-    return __builtin_amdgcn_sicmp(a, b, 38);          // ICMP_SGT
-}
-__device__ __forceinline__ uint64_t mask_not_lt(float a, float b) {
-    return __builtin_amdgcn_fcmpf(a, b, 11);          // FCMP_UGE: !(a < b)
-}
+}  // namespace rtk
 
-// Constant address space (read-only for the whole launch; eligible for scalar loads).
-// (The host pass of hipcc also parses device code; there the qualifier is dropped.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define kconst __attribute__((address_space(4)))
-#else
-#define kconst
-#endif
+// The tracer's device library (scans, culling, camera, ray_color, sample, trace_pixel), shared
+// with rt_aov.hip, rt_sampler.hip and rt_selftest.hip.  Included after the diagnostic macros
+// above: the header defines the ones left undefined as no-ops.
+#include "rt_trace_device.h"
 
-// min(|x|, |y|, |z|) (v_min3_f32 with abs modifiers; NaN channels ignored, as IEEE minNum)
-__device__ __forceinline__ float min_abs3(v3 v) {
-    return fminf(fminf(fabsf(v.x), fabsf(v.y)), fabsf(v.z));
-}
-
-struct Hit {
-    int idx;     // winning sphere, -1 = miss
-    float t;     // its root
-};
-
-// sphere_list_hit (wgsl:164-180) + sphere_hit (wgsl:182-201) without the hit record:
-// only the closest root and its index are tracked; the record (p, normal, face,
-// material) is rebuilt once for the winner, bit-identical to the WGSL's last assignment.
-//
-// The scan walks the list in chunks of 4 spheres.  The 16-byte scan records of the next
-// chunk are fetched with scalar loads while the current chunk is computed (the index is
-// wave-uniform, so the records live in SGPRs and feed the VALU directly).  Per sphere the
-// common (miss) path is 12 VALU ops for the discriminant; the chunk's four "!(D < 0)"
-// tests collapse into one integer max + compare on the float bit patterns (exact: D is
-// never -0, see below), so the root-finding path is entered once per chunk at most.
-
-// Discriminant of wgsl:183-187 for one sphere record g = (center, r*r).
-__device__ __forceinline__ float discriminant(const float4 g, v3 o, v3 d, float a, float& h) {
-    const float ocx = g.x - o.x;                                        // wgsl:183
-    const float ocy = g.y - o.y;
-    const float ocz = g.z - o.z;
-    h = fmaf(ocz, d.z, fmaf(ocy, d.y, ocx * d.x));                      // wgsl:185
-    const float c = fmaf(ocz, ocz, fmaf(ocy, ocy, ocx * ocx)) - g.w;    // wgsl:186
-    return fmaf(h, h, -(a * c));                                        // wgsl:187
-}
-
-// Root selection of wgsl:189-201 for sphere i, given its discriminant.  (Callers only
-// pass indices < count.)  The IEEE sqrt and divisions are kept as the compiler emits them:
-// exact unscaled fast paths with per-lane domain checks measured slower here (the checks
-// and their branches cost more SALU/VALU issue than the shorter sequences save).
-__device__ __forceinline__ void consider(float disc, float h, float a, uint32_t i, float& tmax,
-                                         int& idx) {
-    if (!(disc < 0.0f)) {                                               // wgsl:189
-        const float q = sqrtf(disc);
-        float root = (h - q) / a;
-        if (root <= 0x1.0624dep-10f || tmax <= root) {                  // wgsl:196
-            root = (h + q) / a;
-            if (root <= 0x1.0624dep-10f || tmax <= root) return;        // wgsl:198
-        }
-        tmax = root;
-        idx = (int)i;
-    }
-}
-
-// consider() for camera rays whose domain the host has proven (camera_rays_bounded in
-// rt_abi.cpp): a = |d|^2 in [2^-11, 2^20] and |h|, sqrt(D) <= 2^53 for every sphere.  Then
-// sqrt_core(D + 2^-126) and div_core (ya = the shared reciprocal of a) give the IEEE bits
-// wherever the bits matter: for D >= 2^-96 adding 2^-126 (< half an ulp of D) changes
-// nothing; for D in [0, 2^-96) both sqrt(D) and sqrt_core(D + 2^-126) are below 2^-47, so
-// h -+ q rounds to h when |h| >= 2^-22, and below that both roots are under 0.001 (rejected)
-// with either q; |h -+ q| < 2^-100 gives a root under 2^-89 (rejected) with either quotient;
-// every other quotient is inside div_core's exact domain.  A first root above 0.001 and at
-// or beyond tmax also rejects the second: h + q >= h - q and a > 0 make that root larger
-// still.  The device self-test replays both functions on random grazing and ordinary
-// cases (rt_selftest_fastmath, out[4]).
-__device__ __forceinline__ void consider_fast(float disc, float h, float a, float ya,
-                                              uint32_t i, float& tmax, int& idx) {
-    if (!(disc < 0.0f)) {                                               // wgsl:189
-        const float q = sqrt_core(disc + 0x1p-126f);
-        float root = div_core(h - q, a, ya);
-        if (root <= 0x1.0624dep-10f) {                                  // wgsl:196
-            root = div_core(h + q, a, ya);
-            if (root <= 0x1.0624dep-10f || tmax <= root) return;        // wgsl:198
-        } else if (tmax <= root) {
-            return;
-        }
-        tmax = root;
-        idx = (int)i;
-    }
-}
-
-// "!(D < 0)" for any of K discriminants, on the bit patterns: a float is < 0 exactly
-// when its int32 view is <= 0xFF800000 (-inf) and it is not -0.  D = fma(h, h, -(a*c))
-// with h*h >= +0 and a >= +0 cannot round to -0, so the test is one max-tree and one
-// compare per chunk (max_bits below).
-
-// Exhaustive scan: the reference's linear walk over every sphere (wgsl:169-177).
-
-// max over the int32 views of K discriminants
-template <int K>
-__device__ __forceinline__ int max_bits(const float (&dd)[K]) {
-    int m = __float_as_int(dd[0]);
-#pragma unroll
-    for (int k = 1; k < K; ++k) m = max(m, __float_as_int(dd[k]));
-    return m;
-}
-
-// Chunk sizes: a full-list walk is 4 spheres per s_load_dwordx16 (267 us at K3 against
-// 330 us one sphere at a time).  The list-only kernel (max_depth <= 1) walks the short
-// per-tile candidate lists (2.7 spheres on average at K3) 2 at a time, testing fewer
-// padding records (-2 % at K3; mixing both sizes in one kernel measured slower).
-#ifndef RT_SCAN_CHUNK
-#define RT_SCAN_CHUNK 4
-#endif
-#ifndef RT_LIST_CHUNK
-#define RT_LIST_CHUNK 2
-#endif
-// the bounce instance's camera rays over their tile's list (K5: 2.1 entries per tile)
-#ifndef RT_BOUNCE_LIST_CHUNK
-#define RT_BOUNCE_LIST_CHUNK 2
-#endif
-template <int kScan>
-constexpr int scan_chunk() { return is_list_kernel(kScan) ? RT_LIST_CHUNK : RT_SCAN_CHUNK; }
-// Per-frame stores of fused launches (TraceParams::store_each) in rt_trace_kernel exist in
-// the camera-ray-only instances alone (the culled instance would spill registers for them
-// and runs one frame per launch); the bounce instance (rt_bounce_kernel) has its own
-// two-last-frames stores and fuses frames too (rt_abi.cpp frames_per_launch_for).
-template <int kScan>
-constexpr bool kStoreEach = is_list_kernel(kScan);
-// Exact fast division / sqrt cores (rt_device.h) in the camera-ray-only instances, which
-// rt_abi.cpp selects only for cameras and scenes inside the proven domain
-// (camera_rays_bounded): bit 1 the roots of the scan, 2 the normal, 4 the sky, 8 the
-// metal / dielectric normalisations (the last three behind a wave-wide check of their
-// operands), 16 the defocus disk's reciprocal table (disk_unit).  K3 per frame (fused): 21.7 us without, 20.9 / 20.1 / 20.1 us with bits
-// 1 / 1-2 / 1-4; the accumulator's three divisions by f32(n + 1) the same way (checked
-// numerators in [2^-88, 2^88)) measured +0.75 us and are left to the compiler.
-// The accumulator's division by f32(n + 1) (wgsl:356) where every pixel of the wave holds
-// the hinted count n (the one-frame kernel, the frame groups of trace_pair): a Markstein
-// division by k = f32(n + 1) with y = RN32(1 / k) from the host (acc_rn: a multiply and two
-// fmas per channel; round 5, against round 2's RN32(num * RN64(1 / k)), acc_f64: two
-// conversions and an f64 multiply per channel, each a 4-cycle VALU form).  Exactness: for
-// an integer k < 2^22 (kAccRnMax below), div_rn (rt_device.h) returns the IEEE quotient
-// whenever num and the quotient are normal; numerators in (0, 2^-102) could give subnormal quotients and take the
-// IEEE division (acc_ok: one unsigned compare per channel on the bit patterns; zero passes).
-// Zero, inf and NaN numerators need no exclusion in this use: num = col - c with the sample
-// colour col finite (|col| <= 1: a product of albedos in [0, 1] and the sky's [0.5, 1]) or
-// NaN (a degenerate refraction); -0 / k comes out +0, but num = -0 needs c = +0 and c + (+-0)
-// is +0 either way; num = +-inf needs c = -+inf, and c + num / k and c + div_rn(...) are NaN
-// both (inf - inf); NaN propagates through both.  rt_selftest_fastmath replays it on random
-// accumulators and colours.
-constexpr uint32_t kBits2m102 = 0x0C800000u;   // 2^-102
-// The Markstein step by k = f32(n + 1) is the IEEE quotient for integer k < 2^22 even where
-// q = RN(num y) is 1.5 ulp off (Markstein's hypothesis needs one): num - mid k is a nonzero
-// multiple of ulp(num / k) / 2 for every rounding midpoint mid, so |num / k - mid| >=
-// ulp / (2 k) > 2^-23 ulp, more than the corrected quotient's error |q - num / k| |k y - 1|
-// <= 1.5 ulp 2^-24 (round-5 ADVICE).  Counts of 2^22 or more take the IEEE division.
-constexpr uint32_t kAccRnMax = 1u << 22;
-// |x| >= 2^-102 or x == +-0 (NaN, inf pass) as one unsigned compare per channel on
-// 2 (abs_bits(x) - 1) mod 2^32 = (bits << 1) - 2: the sign shifted out, one v_lshl_add per
-// channel instead of an and and an add (x = +-0 wraps to 0xFFFFFFFE, above the bound, as
-// abs_bits(x) - 1 wraps to 0xFFFFFFFF; otherwise the doubling is exact, abs_bits < 2^31)
-constexpr uint32_t kAccOkDbl = 2u * (kBits2m102 - 1u);
-__device__ __forceinline__ uint32_t dbl_m2(float x) { return (__float_as_uint(x) << 1) - 2u; }
-// (acc_ok(num) == acc_min_bits(num) >= kAccOkDbl)
-__device__ __forceinline__ uint32_t acc_min_bits(v3 num) {
-    return min(min(dbl_m2(num.x), dbl_m2(num.y)), dbl_m2(num.z));
-}
-__device__ __forceinline__ bool acc_ok(v3 num) { return acc_min_bits(num) >= kAccOkDbl; }
-// c + num / k with y = RN32(1 / k)
-__device__ __forceinline__ v3 acc_rn(v3 c, v3 num, float k, float y) {
-    return mk(c.x + div_rn(num.x, k, y), c.y + div_rn(num.y, k, y), c.z + div_rn(num.z, k, y));
-}
-template <int kScan>
-constexpr bool fast_core(int bit) { return is_list_kernel(kScan); }
-// The defocus disk's normalisation in the camera-ray-only trace instances (disk_unit)
-constexpr int kTraceDisk = 3;
-
-// Scan records are read through the constant address space: they do not change during a
-// launch, and only then may the compiler use scalar loads (s_load_dwordx8/16 into SGPRs)
-// in kernels that store images inside the frame loop.  (The single-frame list instance
-// keeps vector loads: its SGPRs are short, scalar records measured +0.6 us per update.)
-template <bool kScalar>
-__device__ __forceinline__ float4 load_rec(const float4* __restrict__ geom, uint32_t i) {
-    if (kScalar) return ((const kconst float4*)geom)[i];
-    return geom[i];
-}
-
-// A tile's candidate count through the constant address space: a scalar load (the lists do
-// not change during a launch), not a vector load + readfirstlane.
-__device__ __forceinline__ uint32_t load_cnt(const float4* cand, uint32_t tile) {
-    return ((const kconst uint32_t*)cand)[(size_t)tile * (4u * kCandStride)];
-}
-
-// kFast: camera rays in the host-proven domain (consider_fast).  kScalar: read the records
-// through the constant address space (below).
-template <int K, bool kFast = false, bool kScalar = true>
-__device__ __forceinline__ Hit scan_exhaustive(const float4* __restrict__ geom, uint32_t count,
-                                               v3 o, v3 d) {
-    float tmax = 0x1.05ed2ep+118f;             // 3.4e35 (wgsl:266)
-    int idx = -1;
-    if (count == 0) return Hit{idx, tmax};
-    const float a = dot(d, d);                 // wgsl:184 (ray-invariant)
-    const float ya = kFast ? rcp_refined(a) : 0.0f;
-    // The record list is zero-padded to whole chunks plus one chunk more (rt_abi.cpp), so
-    // every chunk (and the one-ahead prefetch) is a full scalar load; padding records are
-    // never accepted (consider() is only called for indices < count).
-    float4 cur[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) cur[k] = load_rec<kScalar>(geom, k);
-    for (uint32_t i = 0; i < count; i += K) {
-        float4 nxt[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) nxt[k] = load_rec<kScalar>(geom, i + K + k);
-        float hh[K], dd[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) dd[k] = discriminant(cur[k], o, d, a, hh[k]);
-        if (__builtin_expect(max_bits<K>(dd) > (int)0xFF800000, 0)) {
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-                if (i + k < count) {
-                    if (kFast)
-                        consider_fast(dd[k], hh[k], a, ya, i + k, tmax, idx);
-                    else
-                        consider(dd[k], hh[k], a, i + k, tmax, idx);
-                }
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) cur[k] = nxt[k];
-    }
-    return Hit{idx, tmax};
-}
-
-// ---- Exact wave-level culling --------------------------------------------------------
-//
-// The 64 rays of a wave (one 8x8 tile, plus lens offsets) are nearly coherent.  Bound all
-// of the wave's live rays by one double cone: apex = centroid of the origins, every
-// origin within r_O of it, every unit direction within angle theta of the axis A (either
-// sign).  For sphere (C, R) with v = C - apex, t = v.A, p = |v - tA|, every ray line is at
-// distance >= p cos(theta) - |t| sin(theta) - r_O from C.  In exact arithmetic
-// D = |d|^2 (R^2 - dist^2), and the f32 evaluation of wgsl:183-187 errs by less than
-// ~32 eps |d|^2 (|oc|^2 + R^2) (eps = 2^-24), so the computed D is certainly negative when
-// dist > R + m with m = 2.5e-3 (|oc| + |R|) >= 2.5x sqrt(16 eps)|oc| + sqrt(6 eps)|R|, and
-// |oc| <= |t| + p + r_O + d_max (DESIGN.md §5 has the derivation).
-// Such a sphere can never be the hit of any lane and is skipped; every other sphere goes
-// through the exact per-lane test in list order, so the closest-hit result (including
-// the first-index-wins tie rule) is bit-identical to the exhaustive scan.  One sphere
-// per lane is tested against the cone (64 spheres per VALU instruction); survivors are
-// picked from the ballot mask in increasing index order.  Bounce rays walk the sphere grid
-// instead when the scene has one (scan_grid below); non-finite or degenerate rays, wide
-// cones (theta >~ 60 deg) and short lists use the exhaustive scan.
-constexpr uint32_t kCullMinSpheres = 32;
-
-// Wave-wide reductions on the VALU: row_ror DPP inside each 16-lane row, then the four
-// row results are read into SGPRs (v_readlane) and combined, so every lane receives the
-// same (uniform) value.  Rounding order does not matter here: the cone only needs to be
-// conservative, and the margins of cone_misses() dwarf these errors.
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-constexpr int kRowRor8 = 0x128, kRowRor4 = 0x124, kRowRor2 = 0x122, kRowRor1 = 0x121;
-__device__ __forceinline__ float lane_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp<kRowRor8>(v);
-    v += dpp<kRowRor4>(v);
-    v += dpp<kRowRor2>(v);
-    v += dpp<kRowRor1>(v);
-    return (lane_f(v, 0) + lane_f(v, 16)) + (lane_f(v, 32) + lane_f(v, 48));
-}
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp<kRowRor8>(v));
-    v = fmaxf(v, dpp<kRowRor4>(v));
-    v = fmaxf(v, dpp<kRowRor2>(v));
-    v = fmaxf(v, dpp<kRowRor1>(v));
-    return fmaxf(fmaxf(lane_f(v, 0), lane_f(v, 16)), fmaxf(lane_f(v, 32), lane_f(v, 48)));
-}
-__device__ __forceinline__ bool finite3(v3 v) {
-    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
-}
-
-struct Cone {
-    v3 apex, axis;
-    float cos_t, sin_t, r_o, d_max;
-};
-
-// Builds the cone of the live lanes' rays; false when culling cannot be used.  Must be
-// called with the whole wave active (it reduces across lanes).  The apex is the centroid
-// of the points q = o + d: for camera rays these are the sample points on the focus
-// plane, where the beam of a tile is narrowest; r_o bounds |q - apex| and d_max bounds
-// |d| (so |o - apex| <= r_o + d_max for the rounding margin).
-__device__ __forceinline__ bool wave_cone(v3 o, v3 d, bool live, Cone& k) {
-    const float dd = dot(d, d);
-    const v3 q = add(o, d);
-    const bool bad = live && !(finite3(o) && finite3(q) && dd > 0.0f && __builtin_isfinite(dd));
-    const unsigned long long lm = rt_ballot(live);
-    if (lm == 0ull || rt_ballot(bad)) return false;
-    // Axis and apex come from the first live lane (v_readlane: no cross-lane reduction);
-    // the half-angle, the apex radius and max |d| are then exact max-reductions.
-    const int L = (int)__builtin_ctzll(lm);
-    const float inv = rsqrtf(dd);
-    const v3 u = mk(d.x * inv, d.y * inv, d.z * inv);
-    k.axis = mk(lane_f(u.x, L), lane_f(u.y, L), lane_f(u.z, L));
-    k.apex = mk(lane_f(q.x, L), lane_f(q.y, L), lane_f(q.z, L));
-    const v3 du = sub(u, k.axis), dq = sub(q, k.apex);
-    const float s = wave_max(live ? __builtin_amdgcn_sqrtf(dot(du, du)) : 0.0f);  // chord
-    const float r = wave_max(live ? __builtin_amdgcn_sqrtf(dot(dq, dq)) : 0.0f);
-    const float dm = wave_max(live ? __builtin_amdgcn_sqrtf(dd) : 0.0f);
-    const float su = s * 1.001f + 1e-6f;
-    if (!(su < 1.0f)) return false;                                  // theta >~ 60 degrees
-    k.cos_t = 1.0f - 0.5f * su * su;
-    k.sin_t = su * __builtin_amdgcn_sqrtf(1.0f - 0.25f * su * su) * 1.001f;
-    k.r_o = r * 1.001f + 1e-6f * (fabsf(k.apex.x) + fabsf(k.apex.y) + fabsf(k.apex.z));
-    k.d_max = dm * 1.001f;
-    return true;
-}
-
-// True when sphere record g = (center, r*r) provably misses every ray of the cone.
-// lhs bounds the distance of every ray line from C from below (less 1e-5 of the magnitudes
-// for its own f32 evaluation); the computed discriminant is certainly negative when
-// dist^2 > R^2 + E, E = eps (16 |oc|^2 + 6 R^2), and m^2 >= 6.25e-6 (|oc|^2 +
-// R^2) >= E, so the test is dist > sqrt(R^2 + m^2) — round 4 used R + m, which is larger by
-// up to m, about a fifth of a small sphere's radius at the K3 camera's distances (K3's
-// candidate lists 2.68 -> 2.22 entries per tile, profiles/r05/r05t/).
-__device__ __forceinline__ bool cone_misses(const Cone& k, float4 g) {
-    const v3 v = mk(g.x - k.apex.x, g.y - k.apex.y, g.z - k.apex.z);
-    const float t = dot(v, k.axis);
-    const float p = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-t, t, dot(v, v)), 0.0f));
-    const float at = fabsf(t), R = __builtin_amdgcn_sqrtf(g.w) * 1.0001f;
-    const float mag = at + p + k.r_o;
-    const float lhs = fmaf(p, k.cos_t, -at * k.sin_t) - k.r_o - 1e-5f * mag;
-    const float m = 2.5e-3f * (mag + k.d_max + R);
-    return lhs > R && lhs * lhs > fmaf(R, R, m * m) * 1.0001f;   // NaN anywhere -> keep
-}
-
-// Scan records staged in LDS by the workgroup (culled scan, lists up to kLdsMaxRecords).
-extern __shared__ float4 lds_recs[];
-
-// kLds: read the cull records from the workgroup's LDS copy (else from the global array);
-// both hold count records zero-padded to a multiple of 64.
-// ---- Exact grid walk for incoherent bounce rays ---------------------------------------
-//
-// The closest hit of the linear scan (consider() in index order: a later sphere wins only
-// if strictly nearer) is the minimum over spheres of c_i = root1 if root1 > 0.001, else
-// root2 if root2 > 0.001, with ties going to the lower index: a sphere whose first root is
-// valid but not below the running tmax has a second root at least as large (h + q >= h - q,
-// a > 0), and a tie keeps the earlier index.  So the spheres may be tested in any order with
-// consider_any's rule.  A sphere can be accepted only at a root t > 0 whose point lies
-// within sqrt(R^2 + m^2) of its centre (m the f32 margin of the discriminant, as in the cone
-// test), so the grid walk visits every cell the ray passes through for t >= 0 inside the
-// gridded spheres' slab, and each sphere is registered in every cell within
-// sqrt(R^2 + grid_m^2) + grid_e of its centre (rt_abi.cpp): no sphere that could be accepted
-// is skipped.
-// (items: the grid's item index array — the sphere index items[i] is loaded only for a root
-// that is accepted or ties; null: i is the sphere index)
-__device__ __forceinline__ void consider_any(float disc, float h, float a, uint32_t i,
-                                             float& tmax, int& idx,
-                                             const uint32_t* items = nullptr) {
-    if (!(disc < 0.0f)) {                                               // wgsl:189
-        const float q = sqrtf(disc);
-        float root = (h - q) / a;
-        if (root <= 0x1.0624dep-10f) {                                  // wgsl:196
-            root = (h + q) / a;
-            if (root <= 0x1.0624dep-10f) return;                        // wgsl:198
-        }
-        if (root <= tmax) {
-            const int si = (int)(items ? items[i] : i);
-            if (root < tmax || si < idx) {
-                tmax = root;
-                idx = si;
-            }
-        }
-    }
-}
-// consider_any with consider_fast's arithmetic (sqrt_core of D + 2^-126, div_core with the
-// shared reciprocal ya of a): the IEEE roots wherever they decide anything, on consider_fast's
-// domain (a in [2^-11, 2^20], |h| and sqrt(D) <= 2^53), which roots_fast_wave checks per wave.
-__device__ __forceinline__ void consider_any_fast(float disc, float h, float a, float ya,
-                                                  uint32_t i, float& tmax, int& idx,
-                                                  const uint32_t* items = nullptr) {
-    if (!(disc < 0.0f)) {                                               // wgsl:189
-        const float q = sqrt_core(disc + 0x1p-126f);
-        float root = div_core(h - q, a, ya);
-        if (root <= 0x1.0624dep-10f) {                                  // wgsl:196
-            root = div_core(h + q, a, ya);
-            if (root <= 0x1.0624dep-10f) return;                        // wgsl:198
-        }
-        if (root <= tmax) {
-            const int si = (int)(items ? items[i] : i);
-            if (root < tmax || si < idx) {
-                tmax = root;
-                idx = si;
-            }
-        }
-    }
-}
-// Whether every live ray of the wave is in consider_fast's domain against every sphere of a
-// scene with |C| + |R| <= 2^40 (scene_ok: TraceParams::roots_fast): a = |d|^2 in
-// [2^-11, 2^20] and |o|'s components below 2^39.  Then |oc| <= |C| + |o| < 2^41,
-// |h| <= |d| |oc| < 2^51 and, with c = |oc|^2 - R^2 >= -R^2, sqrt(D) <= sqrt(h^2 + a R^2)
-// < 2^52.  NaN or infinite a / o fail the test.  (Bounce rays and the bounce instance's camera
-// rays: the camera-ray-only instances have the host's camera_rays_bounded instead.)
-__device__ __forceinline__ bool roots_fast_wave(uint32_t scene_ok, v3 o, float a, bool live) {
-    const uint32_t om = max(max(abs_bits(o.x), abs_bits(o.y)), abs_bits(o.z));
-    const bool ok = __float_as_uint(a) - 0x3A000000u <= 0x49800000u - 0x3A000000u &&  // a
-                    om < 0x53000000u;                                               // 2^39
-    return scene_ok != 0u && rt_ballot(live && !ok) == 0ull;
-}
-// The grid's launch parameters (TraceParams grid_*), as one value: built from the kernel
-// argument, or (rt_bounce_kernel) re-read from the kernarg segment at every use so that they
-// do not stay live in SGPRs across the frame loop.
-struct GridP {
-    const uint2* cells;
-    const float4* geom;
-    const uint32_t* items;
-    const uint32_t* big;
-    const float4* sgeom;     // TraceParams::geom (the big spheres' records)
-    uint32_t nx, nz, nbig;
-    float x0, z0, s, inv_s, ylo, yhi, cx, cy, cz, reach, m, e;
-    uint32_t roots_fast;     // TraceParams::roots_fast
-};
-template <typename P>
-__device__ __forceinline__ GridP grid_params(const P& p) {
-    GridP g;
-    g.roots_fast = p.roots_fast;
-    g.cells = p.grid_cells;
-    g.geom = p.grid_geom;
-    g.items = p.grid_items;
-    g.big = p.grid_big;
-    g.sgeom = p.geom;
-    g.nx = p.grid_nx;
-    g.nz = p.grid_nz;
-    g.nbig = p.grid_nbig;
-    g.x0 = p.grid_x0;
-    g.z0 = p.grid_z0;
-    g.s = p.grid_s;
-    g.inv_s = p.grid_inv_s;
-    g.ylo = p.grid_ylo;
-    g.yhi = p.grid_yhi;
-    g.cx = p.grid_cx;
-    g.cy = p.grid_cy;
-    g.cz = p.grid_cz;
-    g.reach = p.grid_reach;
-    g.m = p.grid_m;
-    g.e = p.grid_e;
-    return g;
-}
-// kFast: the roots by consider_any_fast (the wave passed roots_fast_wave; same bits).
-// The walk's own t values (slab and box entry / exit, cell-boundary crossings and their
-// steps) are products with refined reciprocals of d's components (rcp_refined: one Newton
-// step from v_rcp_f32) rather than IEEE quotients: they only steer the traversal, whose cells
-// are padded by e (build_grid).  Each such product is within 1 ulp (<= 2 eps, eps = 2^-24) of
-// its exact value instead of half an ulp, so a crossing after k steps is off by at most
-// (4 + 6k) eps x the coordinate magnitudes (the start and the k additions of the step,
-// each step's own error included), inside e's (k + 16) x 8 eps.  A zero component keeps its
-// branch; a subnormal one gives an infinite or huge reciprocal, i.e. an axis the ray does not
-// cross (it moves less than 2^-60 along it inside the box), or a NaN t that fminf / fmaxf /
-// the compares skip the same way.
-// walk: this lane walks the grid (false: a far ray that misses every small sphere, which only
-// tests the big list; grid_usable).
-template <bool kFast>
-__device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live, bool walk) {
-    const float a = dot(d, d);
-    const float ya = kFast ? rcp_refined(a) : 0.0f;
-    float tmax = 0x1.05ed2ep+118f;             // 3.4e35 (wgsl:266)
-    int idx = -1;
-    auto test = [&](float disc, float h, uint32_t i, const uint32_t* items) {
-        if (kFast)
-            consider_any_fast(disc, h, a, ya, i, tmax, idx, items);
-        else
-            consider_any(disc, h, a, i, tmax, idx, items);
-    };
-    // spheres outside the grid (the ground, large ones): every live lane tests them
-    for (uint32_t b = 0; b < p.nbig; ++b) {
-        const uint32_t i = p.big[b];
-        const float4 g = p.sgeom[i];
-        float h;
-        const float disc = discriminant(g, o, d, a, h);
-        if (live) test(disc, h, i, nullptr);
-    }
-    BCOUNT(26);
-    if (!live || !walk) return Hit{idx, tmax};
-    BCOUNT(kFast ? 0 : 14);
-    // t range of the ray inside the slab and the grid box (t >= 0)
-    const float rx = rcp_refined(d.x), ry = rcp_refined(d.y), rz = rcp_refined(d.z);
-    float t0 = 0.0f, t1 = 0x1.05ed2ep+118f;
-    auto clip = [&](float oc, float dc, float rc, float lo, float hi) {
-        if (dc != 0.0f) {
-            const float ta = (lo - oc) * rc, tb = (hi - oc) * rc;
-            t0 = fmaxf(t0, fminf(ta, tb));
-            t1 = fminf(t1, fmaxf(ta, tb));
-        } else if (oc < lo || oc > hi) {
-            t1 = -1.0f;
-        }
-    };
-    const float xhi = p.x0 + p.s * (float)p.nx;
-    const float zhi = p.z0 + p.s * (float)p.nz;
-    clip(o.y, d.y, ry, p.ylo, p.yhi);
-    clip(o.x, d.x, rx, p.x0, xhi);
-    clip(o.z, d.z, rz, p.z0, zhi);
-    if (!(t0 <= t1)) return Hit{idx, tmax};
-    // 2-D DDA over the cells from P(t0) to P(t1)
-    const int nx = (int)p.nx, nz = (int)p.nz;
-    int ix = (int)floorf((fmaf(t0, d.x, o.x) - p.x0) * p.inv_s);
-    int iz = (int)floorf((fmaf(t0, d.z, o.z) - p.z0) * p.inv_s);
-    ix = min(max(ix, 0), nx - 1);
-    iz = min(max(iz, 0), nz - 1);
-    const int sx = d.x > 0.0f ? 1 : -1, sz = d.z > 0.0f ? 1 : -1;
-    const float inf = 0x1.05ed2ep+118f;
-    float tx = d.x != 0.0f ? (p.x0 + p.s * (float)(ix + (sx > 0)) - o.x) * rx : inf;
-    float tz = d.z != 0.0f ? (p.z0 + p.s * (float)(iz + (sz > 0)) - o.z) * rz : inf;
-    const float dtx = d.x != 0.0f ? p.s * fabsf(rx) : inf;
-    const float dtz = d.z != 0.0f ? p.s * fabsf(rz) : inf;
-    const float slack = 2.0f * p.e * rsqrtf(a) * 1.01f;
-    for (int step = 0; step < nx + nz + 2; ++step) {
-        BCOUNT(2);
-        const uint2 range = p.cells[iz * nx + ix];
-        for (uint32_t k = range.x; k < range.y; ++k) {
-            BCOUNT(4);
-            float h;
-            const float disc = discriminant(p.geom[k], o, d, a, h);
-            test(disc, h, k, p.items);
-        }
-        // A cell entered beyond t1, or beyond the closest hit so far, holds no better hit;
-        // slack: the walk's position error (grid_e, as t) and 1e-4 of t.
-        const float tn = fminf(tx, tz);
-        if (tn > fminf(t1, tmax) * 1.0001f + slack) break;
-        if (tx < tz) {
-            ix += sx;
-            tx += dtx;
-            if (ix < 0 || ix >= nx) break;
-        } else {
-            iz += sz;
-            tz += dtz;
-            if (iz < 0 || iz >= nz) break;
-        }
-    }
-    return Hit{idx, tmax};
-}
-__device__ __forceinline__ Hit scan_grid(const GridP& p, v3 o, v3 d, bool live, bool walk) {
-    if (roots_fast_wave(p.roots_fast, o, dot(d, d), live))
-        return scan_grid_t<true>(p, o, d, live, walk);
-    return scan_grid_t<false>(p, o, d, live, walk);
-}
-
-// The wave may walk the grid: every live ray finite and within reach of the grid margin.
-// A ray farther out (walk false) may still share the wave's walk when it certainly misses
-// every small sphere: it tests the big list only.  The small spheres lie in the ball B(c,
-// reach); sphere i's discriminant is certainly negative where the line passes farther than
-// sqrt(R_i^2 + m_i^2) from C_i, m_i = 2.5e-3 (|o - C_i| + R_i) <= m_far = 2.5e-3 (|o - c| +
-// reach) (the cone test's margin), so a line at least reach + m_far from c misses them all
-// (|C_i - c| + R_i <= reach), and so does a ray whose origin lies past the whole ball (c's
-// projection t < -(reach + m_far): both roots of every small sphere negative).  Evaluated with
-// a 1.01 / 1.001 widening and 1e-5 |o - c| for the f32 rounding of t and of |o - c|^2 - t^2.
-// (K5: 0.038 of every wave-frame fell back to the 500-sphere exhaustive scan for the
-// far ground's bounce rays, profiles/r06/r06v/.)
-__device__ __forceinline__ bool grid_usable(const GridP& p, v3 o, v3 d, bool live, bool& walk) {
-    if (p.nx == 0u) return false;
-    const v3 oc = mk(o.x - p.cx, o.y - p.cy, o.z - p.cz);
-    const float vv = dot(oc, oc);
-    const float dist = __builtin_amdgcn_sqrtf(vv);
-    const float dd = dot(d, d);
-    const bool fin = finite3(o) && finite3(d) && dd >= 0x1p-20f && dd <= 0x1p20f;
-    walk = 2.5e-3f * 1.01f * (dist + p.reach) <= p.m;
-    bool far_miss = false;
-    if (fin && !walk) {
-        const float t = -dot(oc, d) * __builtin_amdgcn_rsqf(dd);   // c along the unit ray
-        const float thr = (p.reach + 2.5e-3f * 1.01f * (dist + p.reach)) * 1.001f + 1e-5f * dist;
-        far_miss = fmaf(-t, t, vv) > fmaf(1e-5f, vv, thr * thr * 1.0001f) || t < -thr;
-    }
-    return rt_ballot(live && !(fin && (walk || far_miss))) == 0ull;
-}
-
-template <bool kLds>
-__device__ __forceinline__ Hit scan_culled(const GridP& gp, const float4* __restrict__ geom,
-                                           uint32_t count, v3 o, v3 d, bool live, bool bounce) {
-    const float4* recs = kLds ? lds_recs : geom;
-    // Bounce rays walk the grid whenever the wave may (measured faster than the cone
-    // culling even for coherent specular waves); camera rays of tiles without a candidate
-    // list keep the cone, whose rays share a narrow beam.
-    bool walk;
-    if (bounce && count >= kCullMinSpheres && grid_usable(gp, o, d, live, walk))
-        return scan_grid(gp, o, d, live, walk);
-    (void)bounce;
-    (void)gp;
-    Cone k;
-    if (count < kCullMinSpheres || !wave_cone(o, d, live, k)) {
-        BCOUNT(bounce ? 18 : 20);
-        return scan_exhaustive<RT_SCAN_CHUNK>(geom, count, o, d);
-    }
-    BCOUNT(bounce ? 22 : 24);
-    const uint32_t lane = threadIdx.x & 63u;
-    const float a = dot(d, d);
-    float tmax = 0x1.05ed2ep+118f;
-    int idx = -1;
-    for (uint32_t base = 0; base < count; base += 64u) {
-        const float4 g = recs[base + lane];
-        const bool keep = (base + lane < count) && !cone_misses(k, g);
-        unsigned long long mask = rt_ballot(keep);
-        while (mask) {                                    // survivors, in index order
-            const int j = __builtin_ctzll(mask);
-            mask &= mask - 1ull;
-            const float4 gs = recs[base + (uint32_t)j];   // broadcast read
-            float h;
-            const float disc = discriminant(gs, o, d, a, h);
-            consider(disc, h, a, base + (uint32_t)j, tmax, idx);
-        }
-    }
-    return Hit{idx, tmax};
-}
-
-// ---- Per-tile candidate lists for camera rays -----------------------------------------
-//
-// Every camera ray of a tile passes through the tile's footprint on the focus plane
-// (pc = vul + pdu*sx + pdv*sy with sx in [x0, x0+8], sy in [y0, y0+8] for any jitter, since
-// rounding is monotonic) and through the lens disk (|o - center| <= |(px,py)| *
-// sqrt(|ddu|^2 + |ddv|^2)), whatever the frame seed.  That gives a cone valid for ALL
-// frames of a camera: apex = footprint centre Pc, r_O = footprint radius, axis =
-// Pc - center, sin(theta) <= (r_O + r_lens) / (|Pc - center| - r_O - r_lens).  Spheres
-// that cone_misses() rejects can never be hit by a camera ray of the tile; the others are
-// listed (records + indices, in index order) once per camera/scene by
-// rt_candidates_kernel, and each frame's camera rays test only that list.
-__device__ __forceinline__ float len3(v3 v) { return __builtin_amdgcn_sqrtf(dot(v, v)); }
-
-// The cone of the camera rays through the focus-plane rectangle of pixel columns [x0, x1)
-// and rows [y0, y1) (one tile: 8 x 8).
-__device__ __forceinline__ bool footprint_cone(const TraceParams& p, float x0, float x1,
-                                               float y0, float y1, Cone& k) {
-    const v3 vul = mk(p.vul[0], p.vul[1], p.vul[2]), pdu = mk(p.pdu[0], p.pdu[1], p.pdu[2]),
-             pdv = mk(p.pdv[0], p.pdv[1], p.pdv[2]);
-    const v3 ctr = mk(p.center[0], p.center[1], p.center[2]);
-    const v3 pc = fmas(0.5f * (y0 + y1), pdv, fmas(0.5f * (x0 + x1), pdu, vul));
-    float rq = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const v3 q = fmas(c & 2 ? y1 : y0, pdv, fmas(c & 1 ? x1 : x0, pdu, vul));
-        rq = fmaxf(rq, len3(sub(q, pc)));
-    }
-    float rl = 0.0f;
-    if (p.defocus_angle > 0.0f) {
-        const v3 du = mk(p.ddu[0], p.ddu[1], p.ddu[2]), dv = mk(p.ddv[0], p.ddv[1], p.ddv[2]);
-        rl = __builtin_amdgcn_sqrtf(dot(du, du) + dot(dv, dv));
-    }
-    const float mag = fabsf(pc.x) + fabsf(pc.y) + fabsf(pc.z) + fabsf(ctr.x) + fabsf(ctr.y) +
-                      fabsf(ctr.z);
-    rq = rq * 1.001f + 1e-5f * mag;                 // f32 evaluation of pc and o = pc - d + d
-    rl = rl * 1.001f + 1e-5f * mag;
-    const v3 w = sub(pc, ctr);
-    const float L = len3(w), delta = rq + rl;
-    if (!(L > 4.0f * delta) || !__builtin_isfinite(L + mag)) return false;
-    k.axis = mk(w.x / L, w.y / L, w.z / L);
-    k.apex = pc;
-    k.sin_t = delta / (L - delta) * 1.01f;
-    k.cos_t = __builtin_amdgcn_sqrtf(1.0f - k.sin_t * k.sin_t) * 0.999f;
-    k.r_o = rq;
-    k.d_max = (L + delta) * 1.001f;
-    return true;
-}
-
-struct Cam {
-    v3 center, vul, pdu, pdv, ddu, ddv;
-    float defocus_angle;
-    float k1s = -0x1.9943f2p-13f, k1c = 0x1.99eb9cp-16f;   // sincos_k's leading coefficients
-};
-template <typename P>
-__device__ __forceinline__ Cam cam_params(const P& p) {
-    Cam cam;
-    cam.center = mk(p.center[0], p.center[1], p.center[2]);
-    cam.vul = mk(p.vul[0], p.vul[1], p.vul[2]);
-    cam.pdu = mk(p.pdu[0], p.pdu[1], p.pdu[2]);
-    cam.pdv = mk(p.pdv[0], p.pdv[1], p.pdv[2]);
-    cam.ddu = mk(p.ddu[0], p.ddu[1], p.ddu[2]);
-    cam.ddv = mk(p.ddv[0], p.ddv[1], p.ddv[2]);
-    cam.defocus_angle = p.defocus_angle;
-    return cam;
-}
-
-// The defocus disk's normalize((cos, sin)) (wgsl:327-331).  Over all 2^32 values of
-// hash(seed + 1), len2 = sa^2 + ca^2 takes only the eight f32 values of
-// [1 - 6*2^-24, 1 + 2^-23], |sa| >= 2^-30 or sa == +0 and |ca| >= 2^-27 (checked
-// exhaustively by rt_selftest_fastmath), so sqrtf(len2) = 1 - m 2^-24 with
-// m = (0x3F800001 - bits(len2)) >> 1 in {3, 3, 2, 2, 1, 1, 0, 0}.
-// kTable: 0 = sqrt_core / div_core (exact on this domain);
-// 3 = all-f32: len = sqrtf(len2) = 1 - m 2^-24 (bits 0x3F800000 - m) and y = RN32(1 / len)
-// = 1 + ((m + 1) >> 1) 2^-23 (m = 1: 1 + 2^-24 + 2^-48 rounds up; m = 3: 1 + 1.5 ulp + 9
-// 2^-48 rounds to 2 ulp) from the bits of len2, then one Markstein step — q0 = RN(a y), the
-// exact residual r = fma(-len, q0, a), q = RN(q0 + r y) — the correctly rounded a / len
-// for a correctly rounded y (checked against the IEEE division for all 2^32 seeds by
-// rt_selftest_fastmath).  Six f32 operations and four integer ones.  (Rounds 2-4 also had
-// an f64 table of RN64(1 / len), per workgroup in LDS or in closed form: the all-f32 form
-// replaced it in the one-frame kernel in round 3 and in the frame groups in round 5 — no
-// table, no barrier at wave start; an 8-rank K3 chain share 2.69 -> 2.65 us per step,
-// profiles/r05/r05h/.)
-template <int kTable>
-__device__ __forceinline__ void disk_unit(float sa, float ca, float& ux, float& uy) {
-    const float len2 = fmaf(sa, sa, ca * ca);
-    if (kTable == 3) {
-        const uint32_t m = (0x3F800001u - __float_as_uint(len2)) >> 1;
-        const float len = __uint_as_float(0x3F800000u - m);
-        const float y = __uint_as_float(0x3F800000u + ((m + 1u) >> 1));
-        const float qx = ca * y, qy = sa * y;
-        ux = fmaf(fmaf(-len, qx, ca), y, qx);
-        uy = fmaf(fmaf(-len, qy, sa), y, qy);
-    } else {
-        const float len = sqrt_core(len2);
-        const float y = rcp_refined(len);
-        ux = div_core(ca, len, y);
-        uy = div_core(sa, len, y);
-    }
-}
-
-// The lens sample's sincos runs without a NaN guard on its quadrant (the angle is finite):
-// K3 14.26 against 14.42 µs per update over three interleaved rounds
-// (profiles/r04/r04q_ab_front_fin.txt).
-// get_ray (wgsl:305-325) with the pixel-invariant hash(hash(x*73) ^ hash(y*51)) part
-// precomputed per pixel: seed = hash(hxy ^ su), su = sample_index*25 + B (wave-uniform
-// when every pixel of the wave holds the same sample count).
-template <int kTable>
-__device__ __forceinline__ void get_ray(const Cam& cam, uint32_t x, uint32_t y, uint32_t hxy,
-                                        uint32_t su, v3& o, v3& d,
-                                        const v3* c0v = nullptr) {
-    const uint32_t seed = hash(hxy ^ su);
-    // rf(v) = f32(hash(v)) * 2^-32 is exact (a power-of-two scale of a value >= 1 or 0), so
-    // the next rounding is the only one: rf - 0.5 is one fma, 2pi * rf one multiply by
-    // 2pi * 2^-32 — the same bits as the two-step forms.
-    const float offx = fmaf((float)hash(seed), 0x1p-32f, -0.5f);         // sample_square
-    const float offy = fmaf((float)hash(seed * seed), 0x1p-32f, -0.5f);  // wgsl:299-303
-    const float sx = ((float)x + 0.5f) + offx;
-    const float sy = ((float)y + 0.5f) + offy;
-    const v3 pc = fmas(sy, cam.pdv, fmas(sx, cam.pdu, cam.vul));
-    // the lens centre in VGPRs (c0v, the copies the lens-less path needs anyway), so that
-    // fma(u, ddu, centre) has one scalar operand (gfx950 VALU: one SGPR per instruction)
-    // instead of a second copy per component; a caller tracing several pixels per lane
-    // passes one copy for all of them
-    v3 c0 = c0v ? *c0v : cam.center;
-    if (!c0v) asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.z));
-    if (cam.defocus_angle > 0.0f) {                     // defocus_disk_sample wgsl:327-331
-        const float ang = (float)hash(seed + 1u) * 0x1.921fb4p-30f;  // 2*3.1415926 * rf
-        float sa, ca, ux, uy;
-        // (ang = f32(hash) * 2pi 2^-32: always finite, so no NaN guard)
-        sincos_k(ang, sa, ca, cam.k1s, cam.k1c, true);
-        disk_unit<kTable>(sa, ca, ux, uy);
-        o = fmas(uy, cam.ddv, fmas(ux, cam.ddu, c0));
-    } else {
-        // (made here: as a plain copy the compiler hoists it ahead of the branch, three
-        // v_mov per pixel on every lens frame)
-        o = c0;
-        asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z));
-    }
-    d = sub(pc, o);
-}
-
-// A zero vector materialised where this is called: the frame loops' colour of a frame that
-// traces nothing.  As a plain constant the compiler hoists its six v_mov ahead of the branch,
-// onto every traced frame (12 per tile-pair frame in rt_tpair_kernel<2>).
-__device__ __forceinline__ v3 zero_v3_here() {
-    float x, y, z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(x));
-    asm volatile("v_mov_b32 %0, 0" : "=v"(y));
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return mk(x, y, z);
-}
-
-// component-wise select of two v3 (a select of whole v3 values can leave them in
-// scratch memory)
-__device__ __forceinline__ v3 sel3(bool c, v3 a, v3 b) {
-    return mk(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z);
-}
-
-// The reciprocal of |v| in the sky's normalize(d).y and in normalize_w comes from the square
-// root's own rsq (sqrt_core_rcp) instead of a second transcendental (v_rcp).  Adopted in
-// round 4 with the one-frame kernel's select skipping, the AND sign test and one record per
-// tile and step (K3 14.95 -> 14.68 µs per update over three interleaved rounds;
-// profiles/r04/r04k_ab_single_variants.txt).
-// normalize(v) = v / sqrt(v.v) (WGSL normalize).  kFast: when every active lane's |v|^2 is
-// in [2^-20, 2^40] (NaN, 0 and inf are not) and its components are >= 2^-100 in
-// magnitude, sqrt_core and div_core with the shared reciprocal of |v| in [2^-10, 2^20]
-// (components <= |v|: inside div_core's exact domain); otherwise the IEEE operations.
-template <bool kFast>
-__device__ __forceinline__ v3 normalize_w(v3 v) {
-    if (kFast) {
-        const float dd = dot(v, v);
-        const uint32_t span = __float_as_uint(dd) - kBits2m20;
-        // (a component below 2^-100: min_abs3 and an ordered compare, as in shade_hit)
-        if ((mask_uge(span, kBits2p40 - kBits2m20) |
-             __builtin_amdgcn_fcmpf(min_abs3(v), 0x1p-100f, 4)) == 0ull) {
-            float y;
-            const float len = sqrt_core_rcp(dd, y);
-            return mk(div_core(v.x, len, y), div_core(v.y, len, y), div_core(v.z, len, y));
-        }
-    }
-    return normalize(v);
-}
-
-// ray_color (wgsl:261-297), executed by the whole wave: `live` marks the lanes whose path
-// is still being traced; the bounce loop runs while any lane is live, and a lane's
-// values are only updated while it is live, so each lane computes exactly its own
-// per-pixel result.
-// uni (wave-uniform): every live lane of the wave holds the hinted sample count of frame
-// f, so the scatter step's random numbers (pixel-independent, see TraceParams::hint_n)
-// come from the host-computed hint_rs table instead of three hashes, a sqrt and a sincos
-// per lane.
-// The hit normal's (p - C) / R (wgsl:209) on div_core's domain (the callers check it),
-// y = rcp_refined(R).  rn (wave-uniform, TraceParams::normal_rn): one Markstein step per
-// component from y is the IEEE quotient for every numerator of the domain (the numerators
-// >= 2^-100, R in [2^-20, 2^20] and |p - C| <= 2^43 keep the quotients normal) — checked
-// exhaustively for every distinct radius of the scene on the device at upload
-// (rt_rcp_check_kernel); otherwise div_core's two.
-__device__ __forceinline__ v3 normal_div(v3 rel, float r, float y, bool rn) {
-    if (rn) return mk(div_rn(rel.x, r, y), div_rn(rel.y, r, y), div_rn(rel.z, r, y));
-    return mk(div_core(rel.x, r, y), div_core(rel.y, r, y), div_core(rel.z, r, y));
-}
-
-// One 16-B buffer load at a byte offset (raw buffer, no format conversion)
-__device__ __forceinline__ float4 buf_f4(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
-                       __uint_as_float(v.w));
-}
-
-template <int kScan>
-__device__ __forceinline__ v3 ray_color(const TraceParams& p, uint32_t tile, uint32_t ncand,
-                                        uint32_t depth, v3 o, v3 d, uint32_t seed, bool live,
-                                        bool uni, uint32_t f) {
-    v3 cf = mk(1.0f, 1.0f, 1.0f);
-    bool black = false;
-    for (uint32_t i = 0; i < depth; ++i) {
-        if (rt_ballot(live) == 0ull) break;
-        // Camera rays of a tile with a candidate list (ncand != kCandNone) test only the
-        // listed spheres: their records are in index order and padded like the full list,
-        // so the same chunk loop applies; hit.idx then indexes the tile's copy of the
-        // sphere records.
-        const bool listed = kScan != kTraceExhaustive && i == 0 && ncand != kCandNone;
-        const float4* blk = p.cand + (size_t)tile * kCandStride;
-        // (one inlined walk for both pointers: two copies measured slower)
-        const Hit hit =
-            (kScan != kTraceCulled || listed)
-                ? scan_exhaustive<scan_chunk<kScan>(), fast_core<kScan>(1), kScan != kTraceList>(
-                      listed ? blk + kCandRecOff : p.geom, listed ? ncand : p.count, o, d)
-            : p.lds_records ? scan_culled<true>(grid_params(p), p.geom, p.count, o, d, live, i > 0)
-                            : scan_culled<false>(grid_params(p), p.geom, p.count, o, d, live, i > 0);
-        const float4* hs = listed ? blk + kCandSphOff : p.sph;
-        if (!live) continue;
-        if (hit.idx < 0) {                                        // wgsl:288-290
-            live = false;
-            continue;
-        }
-        // Hit record of the winner (wgsl:205-218).  The two record loads are per-lane and
-        // depend on the scan; the scatter's random numbers do not depend on the material
-        // (lambertian and metal draw random_unit_vector(sb), dielectric draws rf(sb), its
-        // first component), so they are computed while the loads are in flight.
-        // (buffer loads here, as in single_sample, measured 1.5 % slower in the 8-rank share
-        // kernel: profiles/r06/r06ax/)
-        const float4 pr = hs[2 * hit.idx];          // position, radius
-        const float4 mat = hs[2 * hit.idx + 1];     // material color
-        float r_sb;
-        v3 ruv;
-        if (uni) {
-            const float4 h = p.hint_rs[f * depth + i];
-            r_sb = h.x;
-            ruv = mk(h.y, h.z, h.w);
-        } else {
-            const uint32_t sb = hash(seed + i * 1000u);           // wgsl:268
-            r_sb = rf(sb);
-            ruv = random_unit_vector(r_sb, sb);
-        }
-        const v3 hp = fmas(hit.t, d, o);
-        const v3 C = mk(pr.x, pr.y, pr.z);
-        // wgsl:209: (p - C) / R.  Fast core: |R| in [2^-20, 2^20] (host-proven) and every
-        // hit lane's three numerators >= 2^-100 in magnitude (they are <= 2^43: the hit
-        // lies on a sphere of the bounded scene).
-        const v3 rel = sub(hp, C);
-        v3 outward;
-        if (fast_core<kScan>(2) &&
-            rt_ballot(min_abs3(rel) < 0x1p-100f) == 0ull) {    // (see shade_hit)
-            const float y = rcp_refined(pr.w);
-            outward = normal_div(rel, pr.w, y, p.normal_rn != 0u);
-        } else {
-            outward = divs(rel, pr.w);
-        }
-        const bool front = dot(d, outward) < 0.0f;
-        const v3 n = sel3(front, outward, neg(outward));
-        v3 att = mk(1.0f, 1.0f, 1.0f), nd = d;   // (defined on every path: kept in registers)
-        if (mat.w < -1.0f) {                                      // lambertian wgsl:84-93
-            const v3 dir = add(n, ruv);
-            nd = sel3(dot(dir, dir) < 0x1.0c6f7ap-20f, n, dir);
-            att = mk(mat.x, mat.y, mat.z);
-        } else if (mat.w <= 1.0f) {                               // metal wgsl:95-100
-            constexpr bool kF = fast_core<kScan>(8);
-            const v3 refl = fmas(mat.w, ruv, normalize_w<kF>(reflect(d, n)));
-            if (!(dot(refl, n) > 0.0f)) {                         // wgsl:277-279
-                black = true;
-                live = false;
-                continue;
-            }
-            nd = normalize_w<kF>(refl);
-            att = mk(mat.x, mat.y, mat.z);
-        } else {                                                  // dielectric wgsl:102-135
-            att = mk(1.0f, 1.0f, 1.0f);
-            const float ratio = front ? 1.0f / mat.x : mat.x;
-            constexpr bool kF = fast_core<kScan>(8);
-            const v3 u = normalize_w<kF>(d);
-            const float cos_t = fminf(dot(neg(u), n), 1.0f);
-            const float sin_t = sqrtf(fmaf(-cos_t, cos_t, 1.0f));
-            const bool cannot = ratio * sin_t > 1.0f;
-            const bool refl = cannot || reflectance(cos_t, ratio) > r_sb;
-            nd = normalize_w<kF>(sel3(refl, reflect(u, n), refract(u, n, ratio)));
-        }
-        cf = mul(cf, att);                                        // wgsl:285-286
-        o = hp;
-        d = nd;
-    }
-    if (black) return mk(0.0f, 0.0f, 0.0f);
-    // Sky (wgsl:293-296): only normalize(d).y is used.  Fast core when every lane's |d|^2
-    // is in [2^-20, 2^40] (NaN and 0 are not): sqrt_core is exact there, and so is
-    // div_core(d.y, |d|) for |d.y| >= 2^-100; below that |uy| < 2^-80 and uy + 1 == 1
-    // with either quotient.
-    const float dd = dot(d, d);
-    float uy;
-    if (fast_core<kScan>(4) &&
-        rt_ballot(__float_as_uint(dd) - kBits2m20 >= kBits2p40 - kBits2m20) == 0ull) {
-        // (|d| and its reciprocal from one rsq, as the one-frame kernel's sky: no v_rcp)
-        float y;
-        const float len = sqrt_core_rcp(dd, y);
-        uy = div_core(d.y, len, y);
-    } else {
-        uy = d.y / sqrtf(dd);
-    }
-    const float a = 0.5f * (uy + 1.0f);
-    const float om = 1.0f - a;
-    return mul(cf, mk(fmaf(a, 0.5f, om), fmaf(a, 0x1.666666p-1f, om), fmaf(a, 1.0f, om)));
-}
-
-// One wave = one 8x8 tile of the (local) image; lanes are row-major inside the tile.
-// Control flow is wave-uniform down to the shading (the culled scan reduces across
-// lanes); per-lane conditions of the reference (n < spp, the image bounds) become the
-// `live` flag instead of branches.
-// a colour's three channels as one vector store (LDS slots of the frame groups)
-typedef float f3v __attribute__((ext_vector_type(3)));
-struct TileCoord {
-    uint32_t x, y;
-    size_t idx;
-    bool valid;
-};
-
-// Launch grid: blockIdx.y = local stripe band, blockIdx.x * 4 + wave = tile column.
-__device__ __forceinline__ TileCoord tile_coord(uint32_t width, uint32_t height,
-                                                uint32_t band_first, uint32_t band_step,
-                                                uint32_t tx, uint32_t lband, uint32_t lane) {
-    TileCoord t;
-    t.x = tx * 8u + (lane & 7u);
-    const uint32_t gband = band_first + lband * band_step;
-    t.y = gband * RT_STRIPE_ROWS + (lane >> 3);
-    const uint32_t ly = lband * RT_STRIPE_ROWS + (lane >> 3);
-    t.valid = (t.x < width) && (t.y < height);
-    t.idx = (size_t)ly * width + t.x;
-    return t;
-}
-__device__ __forceinline__ TileCoord tile_coord(const TraceParams& p, uint32_t tx,
-                                                uint32_t lband, uint32_t lane) {
-    return tile_coord(p.width, p.height, p.band_first, p.band_step, tx, lband, lane);
-}
-
-// One sample of one frame for the pixels with `live` set, traced with sample count n
-// (wgsl:352-358 without the accumulation).
-template <int kScan>
-__device__ __forceinline__ v3 sample(const TraceParams& p, const Cam& cam, uint32_t tile,
-                                     uint32_t ncand, const TileCoord& tc, uint32_t hxy,
-                                     uint32_t n, uint32_t B, uint32_t f, bool live, bool uni) {
-    const uint32_t depth = p.depth;
-    const uint32_t seed = 1u + n + B;                             // wgsl:353
-    v3 o, d;
-    get_ray<fast_core<kScan>(16) ? kTraceDisk : 0>(cam, tc.x, tc.y, hxy, seed * 25u + B, o,
-                                                  d);                          // wgsl:311
-    const v3 col = ray_color<kScan>(p, tile, ncand, depth, o, d, seed + 1u, live, uni, f);
-    return col;
-}
-
-// acc: the pixel's loaded accumulator (unused when frame 0 resets it).  Without a hint the
-// count is taken from acc before the first sample; with a hint the first frame is traced
-// with the hinted count while the load is in flight and verified afterwards.
-// kHint = false ignores the hint (counts from acc, full per-pixel random numbers): the
-// frame-group instance's fallback, kept small so that the instance stays within 64 VGPRs.
-template <int kScan, bool kHint = true>
-__device__ __forceinline__ float4 trace_pixel(const TraceParams& p, const Cam& cam,
-                                              uint32_t tile, uint32_t ncand,
-                                              const TileCoord& tc, uint32_t hxy, float4 acc) {
-    const uint32_t spp = p.spp;                                   // wgsl:343
-    v3 c = mk(0.0f, 0.0f, 0.0f);
-    uint32_t n = 0u;
-    bool known = p.reset_first != 0u;                             // wgsl:345-350
-    if (!known && (!kHint || p.hint_frames == 0u)) {
-        c = mk(acc.x, acc.y, acc.z);                              // wgsl:339-341
-        n = f2u(acc.w);
-        known = true;
-    }
-    for (uint32_t f = 0; f < p.frames; ++f) {
-        const uint32_t B = p.seed_b[f];                           // wgsl:311,353
-        if (f == 0 && p.reset_first) {                            // wgsl:345-350
-            c = mk(0.0f, 0.0f, 0.0f);
-            n = 0u;
-        }
-        const bool hinted = kHint && f < p.hint_frames;
-        uint32_t ng = known ? n : p.hint_n[0];   // count to trace with (unknown: f == 0)
-        bool pending = tc.valid;
-        for (;;) {
-            const bool live = pending && ng < spp;                // wgsl:352
-            v3 col = mk(0.0f, 0.0f, 0.0f);
-            if (rt_ballot(live) != 0ull) {
-                const bool uni = hinted && rt_ballot(live && ng != p.hint_n[f]) == 0ull;
-                col = sample<kScan>(p, cam, tile, ncand, tc, hxy, ng, B, f, live, uni);
-            }
-            bool wrong = false;
-            if (!known) {                                         // verify the hint
-                c = mk(acc.x, acc.y, acc.z);
-                n = f2u(acc.w);
-                known = true;
-                wrong = pending && n != ng;
-            }
-            if (pending && !wrong && n < spp) {
-                const float k = (float)(n + 1u);                  // wgsl:356
-                c = mk(c.x + (col.x - c.x) / k, c.y + (col.y - c.y) / k,
-                       c.z + (col.z - c.z) / k);
-                n += 1u;
-            }
-            if (rt_ballot(wrong) == 0ull) break;
-            pending = wrong;                                      // retrace these pixels
-            ng = n;
-        }
-        // Chained updates: frame f's image (wgsl:362-363) lands in the other ping-pong
-        // buffer; the next frame would read it back (u32(f32(n)), wgsl:341) — here the
-        // registers already hold it.  Only the last two frames' images survive the launch
-        // (each buffer keeps the last frame written to it, and nothing reads a tile's
-        // pixels during the launch but its own wave), so only they are stored — or every
-        // frame's (store_each 2, rt_set_frame_images EVERY).
-        if (kStoreEach<kScan> && p.store_each && (p.store_each == 2u || f + 2u >= p.frames) &&
-            tc.valid)
-            ((f & 1u) ? p.out2 : p.out)[tc.idx] = make_float4(c.x, c.y, c.z, (float)n);
-        n = f2u((float)n);
-    }
-    return make_float4(c.x, c.y, c.z, (float)n);                  // wgsl:362
-}
+namespace rtk {
 
 // Frame groups (kTraceListPair, rt_update_frames with every pixel at the hinted count):
 // kFrameGroup waves own the same tile; wave w traces frames f + w of each group of
@@ -1279,14 +211,7 @@ __device__ __forceinline__ void trace_pair(const TraceParams& p, const Cam& cam,
 // with the next tile's accumulator prefetched — into VGPRs, or into LDS with
 // global_load_lds — measured 15-50 % slower: the loop pushes the kernel past 64 VGPRs /
 // into scratch, and the hardware dispatcher already overlaps the waves' HBM phases.)
-// Minimum waves per SIMD the compiler plans registers for.  7 rather than 8: at 8 it caps
-// SGPRs near 80 and spills ~25 of them into VGPR lanes (v_writelane / v_readlane in the
-// frame loop); at 7 the instances use 94 SGPRs and, at <= 64 VGPRs, still run 8 waves per
-// SIMD (the frame-group instance needs 66 VGPRs: 7 waves).  K3: 29.0 vs 30.3 us per
-// single-frame update, 18.2 vs 18.4 us per fused frame.
-#ifndef RT_TRACE_MIN_WAVES
-#define RT_TRACE_MIN_WAVES 7
-#endif
+// (RT_TRACE_MIN_WAVES, the waves per SIMD these instances are planned for: rt_trace_device.h.)
 // Kernel-argument prefetch (single-frame list instance, one tile per wave): the launch
 // parameters a wave reads are spread over ~12 cache lines of the 2.6-KB kernarg segment and
 // the compiler loads each just before its use — a chain of dependent scalar-cache misses at
@@ -3248,353 +2173,6 @@ __global__ __launch_bounds__(256) void rt_present_kernel(const float4* __restric
     }
 }
 
-// ---- Self-test of the exact fast paths (rt_selftest_fastmath) ------------------------
-// cnt[0]: defocus normalisation, all 2^32 values of hash(seed + 1): both disk_unit forms vs
-//         sqrtf and the IEEE divisions (also the eight-value range of len2 disk_unit<3> needs).
-// cnt[1]: div_core_signed vs a / b on random a, b over div_core's domain (rt_device.h:
-//         |b| in [2^-20, 2^33), |a| in [2^-100, 2^91), exponent gap in [-120, 88]; a also
-//         +-0, b also the accumulator's n + 1 up to 2^32) and over [2^-40, 2^40]^2;
-//         div_rn (y = RN32(1 / b)) vs a / b beyond integer denominators (|b| in
-//         [2^-20, 2^20], |a| in [2^-100, 2^43], where |b y - 1| <= 2^-25; half of them with
-//         both significands near 2); and acc_rn vs c + num / k for numerators acc_ok accepts
-//         (finite f32 bits or NaN, many near the subnormal range) and k in [1, 2^22).
-// cnt[2]: sqrt_core vs sqrtf on every finite x >= 2^-96 (exhaustive).
-// cnt[3]: consider_fast vs consider and consider_any_fast vs consider_any (root selection:
-//         tmax and index) on the first n_rand cases of make_root_case below, over the domain
-//         the guards admit (roots_fast_wave and TraceParams::roots_fast: |d|^2 in
-//         [2^-11, 2^20], every origin component below 2^39, |C| + |R| <= 2^40); the cases in
-//         which either pair differs.  rt_selftest_roots counts the same cases per family and
-//         stratum, with what was drawn and what was really compared.
-// cnt[4]: cases run.
-RT_HD uint32_t mix32(uint64_t i, uint32_t salt) {
-    return hash((uint32_t)i ^ hash((uint32_t)(i >> 32) + salt));
-}
-// sign from r's top bit, mantissa from r, exponent e (unbiased; -127: a subnormal)
-RT_HD float with_exp(uint32_t r, int e) {
-    const uint32_t u = (r & 0x807FFFFFu) | ((uint32_t)(127 + e) << 23);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-RT_HD float unit_rand(uint32_t r) {   // [-1, 1)
-    return (float)(int32_t)r * 0x1p-31f;
-}
-__device__ __forceinline__ bool same_bits(float x, float y) {   // NaN == NaN
-    return __float_as_uint(x) == __float_as_uint(y) || (x != x && y != y);
-}
-// One generated ray and sphere.  Case i belongs to stratum i & 3: bit 0 = "far" (|O| or |C|
-// in [2^38, 2^40]), bit 1 = "edge" (a = |d|^2 within one binade of an end of [2^-11, 2^20]).
-// The magnitudes are chosen so that nearly every case lands in the guards' domain and in
-// its stratum by construction; `ok` is the check of both on the values as generated, and
-// only such cases are compared.  (Host and device: plain f32 / f64 arithmetic.)
-struct RootCase {
-    v3 o, d, C;
-    float R, t0;       // t0: the ray parameter of the point the centre was placed beside
-    uint32_t bits;     // random bits for the incoming (tmax, idx) and the item table
-    bool ok;
-};
-RT_HD RootCase make_root_case(uint64_t i) {
-    const bool far = (i & 1u) != 0u, edge = (i & 2u) != 0u;
-    const uint32_t r0 = mix32(i, 11u), r1 = mix32(i, 12u), r2 = mix32(i, 13u),
-                   r3 = mix32(i, 14u), r4 = mix32(i, 15u), r5 = mix32(i, 16u),
-                   r6 = mix32(i, 17u), r7 = mix32(i, 18u), r8 = mix32(i, 19u),
-                   r9 = mix32(i, 20u);
-    // one in sixteen edge cases: a exactly 2^-11 or 2^20 (axis-aligned components)
-    const bool exact = edge && (r0 & 0xFu) == 0u;
-    // far cases, where the large magnitudes sit: 0 = O far with C near it, 1 = C far from a
-    // near O, 2 = O far looking back at a C near the coordinate origin, 3 = O far on one
-    // side and C far on the other (the largest |C - O|, |h| and sqrt(D))
-    const uint32_t mode = ((r0 >> 4) & 3u) & (exact ? 1u : 3u);
-    const bool high = ((r0 >> 6) & 1u) != 0u;
-    const float ta = with_exp(r1 & 0x7FFFFFu,
-                              edge ? (high ? 19 : -11) : -11 + (int)((r0 >> 7) % 31u));
-    // the origin: every component below 2^37 (2^36 beside a far one); far: one in [2^38, 2^39)
-    const bool o_far = far && mode != 1u;
-    const float os = with_exp(0u, -10 + (int)((r0 >> 12) % (far ? 47u : 48u)));
-    v3 o = mk(unit_rand(r2) * os, unit_rand(r3) * os, unit_rand(r4) * os);
-    if (o_far) {
-        const float big = with_exp(r2, 38);
-        const uint32_t ax = r5 % 3u;
-        o = mk(ax == 0u ? big : o.x, ax == 1u ? big : o.y, ax == 2u ? big : o.z);
-    }
-    // the direction: anywhere; in modes 2 and 3 within 2^-3 or less of the way back
-    v3 u = mk(unit_rand(r5), unit_rand(r6), unit_rand(r7));
-    const float ol = sqrtf(dot(o, o));
-    if (o_far && mode >= 2u) {
-        const float w = with_exp(0u, -3 - (int)(r8 % 18u));
-        u = mk(fmaf(w, u.x, -o.x / ol), fmaf(w, u.y, -o.y / ol), fmaf(w, u.z, -o.z / ol));
-    }
-    float us = sqrtf(ta / dot(u, u));
-    if (exact) {
-        const float s0 = (r5 >> 31) ? -1.0f : 1.0f, s1 = (r6 >> 31) ? -1.0f : 1.0f;
-        const float t1 = high ? 0.0f : s1;     // 2^20 = (2^10)^2; 2^-11 = 2 (2^-6)^2
-        const uint32_t ax = r7 % 3u;
-        u = ax == 0u ? mk(s0, t1, 0.0f) : ax == 1u ? mk(0.0f, s0, t1) : mk(t1, 0.0f, s0);
-        us = high ? 0x1p10f : 0x1p-6f;
-    }
-    const v3 d = mk(u.x * us, u.y * us, u.z * us);
-    const float a = dot(d, d);
-    // the radius: half in [2^-20, 2^21), a quarter below (subnormals included), a quarter
-    // above (to 2^36: with the placements below the sphere stays inside 2^40)
-    const uint32_t rc = (r0 >> 20) & 3u;
-    const int er = rc < 2u ? -20 + (int)(r9 % 41u)
-                           : rc == 2u ? -127 + (int)(r9 % 107u) : 21 + (int)(r9 % 15u);
-    float R = with_exp(r3 & 0x7FFFFFu, er);
-    // the point of the ray the centre is placed beside, |t0 d| away from the origin
-    float reach = with_exp(r4 & 0x7FFFFFu, -12 + (int)((r0 >> 26) % (far ? 48u : 50u)));
-    if (far && mode == 1u) reach = with_exp(r4 & 0x7FFFFFu, 38);
-    if (o_far && mode == 2u) reach = ol + unit_rand(r4) * with_exp(0u, 36);
-    if (o_far && mode == 3u) reach = ol + with_exp(r4 & 0x7FFFFFu, 38);
-    // (one in eight behind the origin, where that keeps the placement)
-    const bool behind = ((r8 >> 18) & 7u) == 0u && !(o_far && mode >= 2u);
-    const float t0 = behind ? -reach / sqrtf(a) : reach / sqrtf(a);
-    const v3 P = mk(fmaf(t0, d.x, o.x), fmaf(t0, d.y, o.y), fmaf(t0, d.z, o.z));
-    // sideways from it: by R (1 + 2^-j) to either side of grazing, anywhere inside the sphere,
-    // or (a quarter of the large radii) anywhere, with the radius that brings |C| + R to
-    // 2^40 (1 - 2^-j): the scene bound's end, evaluated in double as rt_abi.cpp does
-    v3 side = mk(unit_rand(r4 ^ r2), unit_rand(r5 ^ r3), unit_rand(r6 ^ r4));
-    const float sd = dot(side, d) / a;
-    side = sub(side, mk(sd * d.x, sd * d.y, sd * d.z));           // ~perpendicular to d
-    const float sl = sqrtf(dot(side, side));
-    const bool graze = ((r8 >> 21) & 1u) != 0u;
-    const bool brim = !graze && rc == 3u && ((r8 >> 22) & 1u) != 0u;
-    const float jitter = 1.0f + unit_rand(r5) * with_exp(0u, -(int)(r1 % 31u));
-    const float k = (brim ? unit_rand(r7) * with_exp(0u, (int)((r8 >> 23) % 36u))
-                          : graze ? R * jitter : R * fabsf(unit_rand(r7))) / sl;
-    const v3 C = mk(fmaf(k, side.x, P.x), fmaf(k, side.y, P.y), fmaf(k, side.z, P.z));
-    const double cl = sqrt((double)C.x * C.x + (double)C.y * C.y + (double)C.z * C.z);
-    if (brim) {
-        const double want = 0x1p40 * (1.0 - (double)with_exp(0u, -1 - (int)((r8 >> 8) % 40u))) - cl;
-        if (want > 0.0 && (double)(float)want <= want) R = (float)want;   // (else as drawn)
-    }
-    const double om = fmax(fmax(fabs((double)o.x), fabs((double)o.y)), fabs((double)o.z));
-    const double far_of = fmax(sqrt((double)o.x * o.x + (double)o.y * o.y + (double)o.z * o.z), cl);
-    RootCase c;
-    c.o = o;
-    c.d = d;
-    c.C = C;
-    c.R = R;
-    c.t0 = t0;
-    c.bits = mix32(i, 21u);
-    c.ok = a >= 0x1p-11f && a <= 0x1p20f && om < 0x1p39 && R >= 0.0f && cl + (double)R <= 0x1p40 &&
-           sl > 0.0f && (!far || (far_of >= 0x1p38 && far_of <= 0x1p40)) &&
-           (!edge || a <= 0x1p-10f || a >= 0x1p19f);
-    return c;
-}
-// The grid's item array in miniature (consider_any's `items`: slot -> sphere index)
-__device__ const uint32_t kRootItems[8] = {5u, 2u, 9u, 0u, 7u, 3u, 11u, 1u};
-struct RootResult {
-    bool ok, rooted, bad_fast, bad_any;
-};
-// Case i through both root selections and their IEEE originals.  The incoming tmax: the
-// scan's sentinel, |t0| (between the sphere's two roots), |t0| / 2 (below them), or a tie —
-// the root the IEEE selection accepts from the sentinel, itself or one of its two neighbours
-// (itself: consider's "tmax <= root" rejects and consider_any's "si < idx" decides, so a fast
-// root one ulp off flips the answer).  consider_any's incoming idx is the sphere's own
-// index + 1 or - 1, its index read from the item table or the slot itself.
-__device__ __forceinline__ RootResult root_case(uint64_t i) {
-    const RootCase c = make_root_case(i);
-    RootResult res = {c.ok, false, false, false};
-    if (!c.ok) return res;
-    const float a = dot(c.d, c.d);
-    const float ya = rcp_refined(a);
-    float h;
-    const float disc = discriminant(make_float4(c.C.x, c.C.y, c.C.z, c.R * c.R), c.o, c.d, a, h);
-    res.rooted = !(disc < 0.0f);
-    float tr = 0x1.05ed2ep+118f;
-    int ir = -1;
-    consider(disc, h, a, 3u, tr, ir);
-    const uint32_t tk = c.bits & 3u;
-    float t_in = tk == 0u ? 0x1.05ed2ep+118f : tk == 1u ? fabsf(c.t0) : fabsf(c.t0) * 0.5f;
-    if (tk == 3u) {
-        const uint32_t nb = (c.bits >> 2) & 3u;       // 0, 1: the root; 2: above; 3: below
-        t_in = ir < 0 ? fabsf(c.t0)
-                      : __uint_as_float(__float_as_uint(tr) + (nb == 2u ? 1u : nb == 3u ? ~0u : 0u));
-    }
-    {
-        float t1 = t_in, t2 = t_in;
-        int i1 = 7, i2 = 7;
-        consider(disc, h, a, 3u, t1, i1);
-        consider_fast(disc, h, a, ya, 3u, t2, i2);
-        res.bad_fast = !(same_bits(t1, t2) && i1 == i2);
-    }
-    {
-        const uint32_t* items = (c.bits & 0x10u) ? kRootItems : nullptr;
-        const uint32_t slot = (c.bits >> 5) & 7u;
-        const int si = (int)(items ? kRootItems[slot] : slot);
-        const int i_in = (c.bits & 0x100u) ? si + 1 : si - 1;
-        float t1 = t_in, t2 = t_in;
-        int i1 = i_in, i2 = i_in;
-        consider_any(disc, h, a, slot, t1, i1, items);
-        consider_any_fast(disc, h, a, ya, slot, t2, i2, items);
-        res.bad_any = !(same_bits(t1, t2) && i1 == i2);
-    }
-    return res;
-}
-// rt_selftest_roots: cnt[(family * kRootStrata + stratum) * 4 + {mismatches, drawn, compared,
-// rooted}].  The grid's stride is a multiple of four, so a thread's cases share a stratum.
-__global__ __launch_bounds__(256) void rt_selftest_roots_kernel(unsigned long long* cnt,
-                                                                uint64_t n_rand) {
-    unsigned long long drawn = 0, compared = 0, rooted = 0, bad_fast = 0, bad_any = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t i = first; i < n_rand; i += stride) {
-        const RootResult r = root_case(i);
-        ++drawn;
-        compared += r.ok;
-        rooted += r.rooted;
-        bad_fast += r.bad_fast;
-        bad_any += r.bad_any;
-    }
-    const uint32_t stratum = (uint32_t)first & (kRootStrata - 1u);
-    for (uint32_t f = 0; f < kRootFamilies; ++f) {
-        unsigned long long* c = cnt + (f * kRootStrata + stratum) * 4u;
-        atomicAdd(&c[0], f == 0u ? bad_fast : bad_any);
-        atomicAdd(&c[1], drawn);
-        atomicAdd(&c[2], compared);
-        atomicAdd(&c[3], rooted);
-    }
-}
-__global__ __launch_bounds__(256) void rt_selftest_kernel(unsigned long long* cnt, uint64_t n_rand) {
-    unsigned long long bad0 = 0, bad1 = 0, bad2 = 0, bad3 = 0, runs = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32);
-         i += stride) {
-        const float ang = 0x1.921fb4p+2f * rf((uint32_t)i);
-        float sa, ca;
-        sincos_c(ang, sa, ca);
-        const float len_ref = sqrtf(fmaf(sa, sa, ca * ca));
-        const float ux_ref = ca / len_ref, uy_ref = sa / len_ref;
-        float ux, uy, fx, fy;
-        disk_unit<0>(sa, ca, ux, uy);
-        disk_unit<3>(sa, ca, fx, fy);
-        bad0 += (__float_as_uint(fx) != __float_as_uint(ux_ref)) ||
-                (__float_as_uint(fy) != __float_as_uint(uy_ref)) ||
-                (__float_as_uint(ux) != __float_as_uint(ux_ref)) ||
-                (__float_as_uint(uy) != __float_as_uint(uy_ref));
-        const float x = __uint_as_float((uint32_t)i);
-        if ((uint32_t)i >= 0x0F800000u && (uint32_t)i < 0x7F800000u)   // [2^-96, +inf)
-            bad2 += __float_as_uint(sqrt_core(x)) != __float_as_uint(sqrtf(x));
-        ++runs;
-    }
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rand; i += stride) {
-        const uint32_t r0 = mix32(i, 1u), r1 = mix32(i, 2u), r2 = mix32(i, 3u);
-        float a, b;
-        if (r2 & 0x40000000u) {                       // the general domain
-            const int eb = -20 + (int)(r2 % 53u);
-            int ea = -100 + (int)((r2 >> 8) % 191u);
-            ea = max(eb - 120, min(eb + 88, ea));
-            a = with_exp(r0, ea);
-            b = with_exp(r1, eb);
-        } else {                                      // [2^-40, 2^40]^2
-            a = with_exp(r0, -40 + (int)(r2 % 80u));
-            b = with_exp(r1, -40 + (int)((r2 >> 8) % 80u));
-        }
-        if ((r2 & 0x70000u) == 0) a = (r0 & 1u) ? -0.0f : 0.0f;
-        if ((r2 & 0x380000u) == 0)                    // n + 1 counts, n < 2^32 - 1
-            b = (float)((r2 & 0x400000u) ? 1u + (r1 & 0xFFFFFFu) : max(r1, 1u));
-        bad1 += !same_bits(div_core_signed(a, b, rcp_refined(b)), a / b);
-        {   // root selection: both families on case i (compared only inside the domain)
-            const RootResult rr = root_case(i);
-            bad3 += rr.bad_fast || rr.bad_any;
-        }
-        {   // the sky's d.y / |d| with |d| and its reciprocal from one rsq (sqrt_core_rcp):
-            // |d|^2 in [2^-20, 2^40], |d.y| <= |d| (and >= 2^-100 or zero)
-            const float dd = with_exp(r1 & 0x7FFFFFu, -20 + (int)(r2 % 60u));
-            float y;
-            const float len = sqrt_core_rcp(dd, y);
-            const float dy = (r0 & 0x1000u) ? 0.0f : unit_rand(r0) * len;
-            if (dd <= 0x1p40f && (dy == 0.0f || fabsf(dy) >= 0x1p-100f))
-                bad1 += !same_bits(div_core(dy, len, y), dy / sqrtf(dd));
-        }
-        {   // div_rn with real denominators where Markstein's hypothesis holds: y = RN32(1 / b)
-            // and |b y - 1| <= 2^-25, so q = RN(a y) is within an ulp of a / b; every other
-            // case the kernels' callers rule out (the radii are checked exhaustively at
-            // upload, rt_rcp_check_kernel; the accumulator's k is an integer < 2^22).  Half
-            // the cases in the corner where |b y - 1| approaches 2^-24: divisor significands
-            // in [1.99, 2), numerator significands within 2^-11 of 2.
-            const bool corner = (r2 >> 20) & 1u;
-            const uint32_t mb = corner ? 0x7EB852u + r1 % (0x800000u - 0x7EB852u) : r1;
-            const uint32_t ma = corner ? 0x7FFFFFu - (r0 % 4096u) : (r0 ^ r2);
-            const float rb = with_exp((r1 & 0x80000000u) | (mb & 0x7FFFFFu), -20 + (int)(r2 % 41u));
-            const float ra = with_exp((r0 & 0x80000000u) | (ma & 0x7FFFFFu),
-                                      -100 + (int)((r2 >> 8) % 144u));
-            const float yb = 1.0f / rb;
-            if (fabsf(fmaf(rb, yb, -1.0f)) <= 0x1p-25f)
-                bad1 += !same_bits(div_rn(ra, rb, yb), ra / rb);
-        }
-        // the accumulator's Markstein division: any finite f32 numerator or NaN (r0's bits:
-        // zeros and subnormals included; the kernels' num = col - c is never +-inf against a
-        // finite c, see acc_ok), k = f32(n + 1) for n + 1 in [1, 2^22) (kAccRnMax)
-        const uint32_t kk = (r2 & 0x800000u) ? 1u + (r1 % (kAccRnMax - 1u))
-                                             : 1u + (r1 % 4096u);   // small counts too
-        const v3 num = mk(__uint_as_float(r0), __uint_as_float(r0 ^ r1),
-                          __uint_as_float(r2 & 0x83FFFFFFu));       // (many tiny ones)
-        if (acc_ok(num) && !isinf(num.x) && !isinf(num.y) && !isinf(num.z)) {
-            const float kf = (float)kk;
-            const v3 c0 = mk(0.0f, 0.0f, 0.0f);
-            const v3 q = acc_rn(c0, num, kf, 1.0f / kf);
-            bad1 += !same_bits(q.x, 0.0f + num.x / kf) || !same_bits(q.y, 0.0f + num.y / kf) ||
-                    !same_bits(q.z, 0.0f + num.z / kf);
-        }
-        ++runs;
-    }
-    atomicAdd(&cnt[0], bad0);
-    atomicAdd(&cnt[1], bad1);
-    atomicAdd(&cnt[2], bad2);
-    atomicAdd(&cnt[3], bad3);
-    atomicAdd(&cnt[4], runs);
-}
-
-// TraceParams::normal_rn: is one Markstein step from y = rcp_refined(R) the IEEE quotient
-// a / R for every numerator the kernels divide, for every distinct radius R of the scene?
-// Markstein's theorem needs y within half an ulp of 1 / R AND q = RN(a y) within one ulp of
-// a / R; a correctly rounded y alone gives |R y - 1| <= 2^-24, and with a divisor's and a
-// quotient's significands both near 2 q can then be 1.5 ulp off (round-5 ADVICE).  So the
-// check is exhaustive instead of sufficient: for each radius every numerator significand
-// (2^23 of them) in two binades, [1, 2) and [2^-100, 2^-99) (the kernels' smallest
-// numerators), against the IEEE division.  A step and its operands scale exactly by powers of
-// two while q, the residual and the result stay normal (numerators in [2^-100, 2^43], R in
-// [2^-20, 2^20]: the callers' domain), so these two binades cover every numerator; the sign
-// is symmetric.  One thread per (radius, significand, binade), a vector atomic OR on a miss.
-constexpr uint32_t kRcpCheckPerRadius = 2u << 23;
-__global__ __launch_bounds__(256) void rt_rcp_check_kernel(const float* radii, uint32_t n,
-                                                           uint32_t* bad) {
-    const uint64_t total = (uint64_t)n * kRcpCheckPerRadius;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint32_t miss = 0u;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const float r = radii[i / kRcpCheckPerRadius];
-        const uint32_t j = (uint32_t)(i % kRcpCheckPerRadius);
-        // significand j & 0x7FFFFF; binade 2^0 or 2^-100
-        const float a = __uint_as_float(((j >> 23) ? 0x0D800000u : 0x3F800000u) | (j & 0x7FFFFFu));
-        const float y = rcp_refined(r);
-        miss |= __float_as_uint(div_rn(a, r, y)) != __float_as_uint(a / r);
-    }
-    if (miss) atomicOr(bad, 1u);
-}
-hipError_t launch_rcp_check(const float* radii, uint32_t n, uint32_t* bad, hipStream_t stream) {
-    if (n == 0u) return hipSuccess;
-    hipLaunchKernelGGL(rt_rcp_check_kernel, dim3(2048), dim3(256), 0, stream, radii, n, bad);
-    return hipGetLastError();
-}
-
-hipError_t launch_selftest(unsigned long long* cnt, uint64_t n_rand, hipStream_t stream) {
-    hipLaunchKernelGGL(rt_selftest_kernel, dim3(8192), dim3(256), 0, stream, cnt, n_rand);
-    return hipGetLastError();
-}
-hipError_t launch_selftest_roots(unsigned long long* cnt, uint64_t n_rand, hipStream_t stream) {
-    // (256 x 2048 threads: a multiple of kRootStrata, see the kernel)
-    hipLaunchKernelGGL(rt_selftest_roots_kernel, dim3(2048), dim3(256), 0, stream, cnt, n_rand);
-    return hipGetLastError();
-}
-
-// 256-thread workgroups: 4 waves = 4 tiles along a stripe band; grid (columns/4, bands).
-static dim3 tile_grid(const TraceParams& p, uint32_t waves = 4) {
-    const uint32_t tiles_x = (p.width + 7u) >> 3;
-    return dim3((tiles_x + waves - 1u) / waves, p.local_bands);
-}
-
 // Launches through hipModuleLaunchKernel with the arguments packed in the kernel's layout and
 // a function handle cached per device and kernel (the launch_single path below): no
 // per-launch symbol lookup or per-argument marshalling of the 2.6-KB TraceParams block.
@@ -4025,315 +2603,6 @@ hipError_t launch_present(const float4* in, uchar4* out, uint64_t texels,
     else
         hipLaunchKernelGGL(rt_present_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0,
                            stream, in, out, texels, srgb_t);
-    return hipGetLastError();
-}
-
-// ---- First-hit G-buffer (rt_aov.h) ---------------------------------------------------
-//
-// One wave per 8x8 tile, lanes row-major inside the tile and the packed stripe map of
-// rt_trace_kernel (tile_coord).  Each lane traces the ray through its pixel's centre from
-// camera.center — get_ray (wgsl:305-325) with both offsets 0 and no lens — with the exact
-// scans of the progressive render, and writes the winner's hit record (wgsl:205-218) out
-// instead of shading it.  Culling is the per-wave cone over the uploaded records
-// (scan_culled with bounce = false: scenes under kCullMinSpheres and degenerate or non-finite
-// waves walk the whole list); the per-tile candidate lists carry no sphere index and belong to
-// the render's camera, so they are not read.  Lanes outside the image are not live for the
-// cone's reductions and store nothing.  The normal is the plain IEEE (p - C) / R: three
-// divisions per pixel beside a scan, and valid for every radius.
-__global__ __launch_bounds__(256) void rt_aov_kernel(const AovParams p) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t tiles_x = (p.width + 7u) >> 3;
-    const uint32_t tx = p.tx0 + blockIdx.x * (blockDim.x >> 6) + wave;
-    if (tx >= tiles_x) return;                                    // whole wave exits
-    const TileCoord tc = tile_coord(p.width, p.height, p.bands & 0xFFFFu,
-                                    (p.bands >> 16) & 0x7FFFu, tx, blockIdx.y, lane);
-    const bool live = tc.valid;
-    const v3 o = mk(p.center[0], p.center[1], p.center[2]);
-    const float sx = (float)tc.x + 0.5f, sy = (float)tc.y + 0.5f;
-    const v3 pc = fmas(sy, mk(p.pdv[0], p.pdv[1], p.pdv[2]),
-                       fmas(sx, mk(p.pdu[0], p.pdu[1], p.pdu[2]),
-                            mk(p.vul[0], p.vul[1], p.vul[2])));
-    const v3 d = sub(pc, o);
-    Hit h;
-    if (p.culled) {
-        const GridP none = {};                                    // (bounce rays only)
-        h = scan_culled<false>(none, p.geom, p.count, o, d, live, false);
-    } else {
-        h = scan_exhaustive<RT_SCAN_CHUNK>(p.geom, p.count, o, d);
-    }
-    const bool hit = live && h.idx >= 0;
-    float4 pr = make_float4(0.0f, 0.0f, 0.0f, 0.0f), mat = pr;
-    if (hit) {
-        pr = p.sph[2 * h.idx];                                    // position, radius
-        mat = p.sph[2 * h.idx + 1];                               // material color
-    }
-    const v3 hp = fmas(h.t, d, o);                                // wgsl:205
-    const v3 outward = divs(sub(hp, mk(pr.x, pr.y, pr.z)), pr.w); // wgsl:206
-    const bool front = dot(d, outward) < 0.0f;                    // wgsl:159-160
-    const v3 n = sel3(front, outward, neg(outward));
-    // which planes are wanted is wave-uniform: a plane not wanted costs no store
-    const bool store = p.pick ? lane + 1u == p.pick : live;
-    const size_t at = p.pick ? 0 : tc.idx;
-    if (!store) return;
-    if (p.id) p.id[at] = hit ? (uint32_t)h.idx : 0xFFFFFFFFu;
-    if (p.hit)
-        p.hit[at] = hit ? make_float4(hp.x, hp.y, hp.z, h.t)
-                        : make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
-    if (p.normal)
-        p.normal[at] = hit ? make_float4(n.x, n.y, n.z, front ? 1.0f : 0.0f)
-                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (p.material) p.material[at] = mat;
-}
-
-hipError_t launch_aov(const AovParams& p, uint32_t tiles_x, uint32_t bands, hipStream_t stream) {
-    if (tiles_x == 0 || bands == 0) return hipSuccess;
-    // four tiles of a band per workgroup, as rt_trace_kernel; a lone tile (rt_pick) is one wave
-    const uint32_t waves = tiles_x == 1u ? 1u : 4u;
-    hipLaunchKernelGGL(rt_aov_kernel, dim3((tiles_x + waves - 1u) / waves, bands),
-                       dim3(64u * waves), 0, stream, p);
-    return hipGetLastError();
-}
-
-// ---- Adaptive sampling (rt_adaptive.h) -----------------------------------------------
-//
-// One `update` in which only the pixels whose error estimate is still above the tolerance
-// take a sample.  One wave per 8x8 tile on rt_trace_kernel's stripe map (tile_coord), four
-// tiles of a band per workgroup.  The wave loads its accumulator texels and error values,
-// decides per lane (rt_adaptive.h: the reset, min_samples, the tolerance, the spp cap), forms
-// the tile's mask with one ballot and lane 0 stores the word.  A wave whose ballot is empty
-// writes its texels back as they pass through and ends: it reads no candidate list, hash table
-// or sphere record.  Any other wave traces one sample with the mask as the per-lane `live` flag
-// — trace_pixel's mechanism for n < spp — through sample<kScan> and ray_color as they are,
-// without a sample-count hint (uni = false: the counts differ per pixel), and accumulates with
-// the reference's IEEE division (wgsl:356), so a sampled texel has rt_update's bits.
-// kScan: kTraceExhaustive, kTraceList (depth <= 1, camera in the proven domain: the fast
-// cores) or kTraceCulled (candidate lists for camera rays, cone / grid culling for bounce rays
-// in ray_color; no LDS copy of the records: TraceParams::lds_records is 0 here).
-template <int kScan>
-__global__ __launch_bounds__(256, RT_TRACE_MIN_WAVES) void rt_adaptive_kernel(
-    const TraceParams p, const AdaptiveParams a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t tiles_x = (p.width + 7u) >> 3;
-    const uint32_t tx = blockIdx.x * 4u + wave;
-    if (tx >= tiles_x) return;                                    // whole wave exits
-    const uint32_t lband = blockIdx.y;
-    const TileCoord tc = tile_coord(p, tx, lband, lane);
-    const uint32_t tile = lband * tiles_x + tx;
-    // (a lane off the image reads texel 0 of the local buffers and stores nothing)
-    const size_t at = tc.valid ? tc.idx : 0;
-    const float4 I = p.in[at];
-    const float err = a.error[at];
-    const uint32_t spp = p.spp;                                   // wgsl:343
-    v3 c = mk(0.0f, 0.0f, 0.0f);
-    uint32_t n = 0u;
-    bool sampled = 0u < spp;                                      // a reset: wgsl:345-350
-    if (!p.reset_first) {
-        c = mk(I.x, I.y, I.z);                                    // wgsl:339-341
-        n = f2u(I.w);
-        const float lm = (0.2126f * I.x + 0.7152f * I.y) + 0.0722f * I.z;
-        const float thr = a.abs_tolerance2 + a.rel_tolerance2 * (lm * lm);
-        const bool converged = n >= a.min_samples && err <= thr;  // (a NaN: not converged)
-        sampled = n < spp && !converged;
-    }
-    sampled = sampled && tc.valid;
-    const uint64_t m = rt_ballot(sampled);
-    if (a.tile_mask && lane == 0u) a.tile_mask[tile] = m;
-    if (m != 0ull) {
-        const uint32_t ncand =
-            (kScan != kTraceExhaustive && p.cand) ? load_cnt(p.cand, tile) : kCandNone;
-        const uint32_t hxy =
-            p.hx[min(tc.x, p.width - 1u)] ^ p.hy[min(tc.y, p.height - 1u)];
-        const Cam cam = cam_params(p);
-        const v3 col = sample<kScan>(p, cam, tile, ncand, tc, hxy, n, p.seed_b[0], 0u, sampled,
-                                     false);
-        if (sampled) {
-            const float k = (float)(n + 1u);                      // wgsl:356
-            c = mk(c.x + (col.x - c.x) / k, c.y + (col.y - c.y) / k, c.z + (col.z - c.z) / k);
-            n += 1u;
-        }
-    }
-    // wgsl:362-363; a texel that passes through is what spp = 0 would write: u32(alpha) again
-    if (tc.valid) p.out[tc.idx] = make_float4(c.x, c.y, c.z, (float)n);
-}
-
-hipError_t launch_adaptive(const TraceParams& p, const AdaptiveParams& a, int kernel,
-                           hipStream_t stream) {
-    const dim3 grid = tile_grid(p);
-    if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    if (kernel == kTraceList)
-        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceList>, grid, dim3(256), 0, stream, p, a);
-    else if (kernel == kTraceCulled)
-        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceCulled>, grid, dim3(256), 0, stream, p, a);
-    else if (kernel == kTraceExhaustive)
-        hipLaunchKernelGGL(rt_adaptive_kernel<kTraceExhaustive>, grid, dim3(256), 0, stream, p,
-                           a);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// ---- Fused adaptive rounds (rt_converge.h) ---------------------------------------------
-//
-// p.frames rounds of rt_adaptive_error, rt_update_adaptive and rt_moments_update over one tile
-// in one launch, beside rt_adaptive_kernel for that kernel's reason (sample<kScan> and
-// ray_color as they are) and on its grid: one wave per 8x8 tile, four tiles of a band per
-// workgroup.  The wave loads its accumulator and moments texels once, keeps both in registers
-// over the frames and stores them once, in place (p.out; nothing reads a tile's texels during
-// the launch but its own wave).  Each frame, in f32 and in the headers' order of operations:
-// the error from the moments and the count (rt_adaptive.h), the decision and its ballot, one
-// sample with the ballot's lanes live when it is not empty (seed_b[f]; no hint), the IEEE
-// division of wgsl:356, and rt_variance.h's four rules on the texel before and after the frame.
-// Control flow is wave-uniform (ballots); the per-lane rules are selects.
-//
-// Early exit: a frame that is not a reset, in which no lane was sampled and
-// which left every on-image lane's accumulator and moments texels bit-identical to what it
-// read, is a fixed point: every later frame reads the same state, decides the same (only the
-// seed differs, and no idle lane reads it) and writes the same.  The wave leaves the loop
-// there.  "No lane sampled" alone would not do: a count of 7.5 passes through as 7, rule 4 then
-// zeroes the moments, the error becomes +inf and the pixel is sampled in the next frame.
-// A wave none of whose frames changed a bit stores no texel.
-// The culled instance holds eight more live registers than rt_adaptive_kernel's across ray_color's
-// culled scans: planned for RT_TRACE_MIN_WAVES it spills to scratch (44 bytes per lane), so it is
-// planned for 6 waves per SIMD (74 VGPRs, no scratch); the other two fit as they are.
-template <int kScan>
-constexpr int converge_min_waves() {
-    return kScan == kTraceCulled ? 6 : RT_TRACE_MIN_WAVES;
-}
-template <int kScan>
-__global__ __launch_bounds__(256, converge_min_waves<kScan>()) void rt_converge_kernel(
-    const TraceParams p, const ConvergeParams a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t tiles_x = (p.width + 7u) >> 3;
-    const uint32_t tx = blockIdx.x * 4u + wave;
-    if (tx >= tiles_x) return;                                    // whole wave exits
-    const uint32_t lband = blockIdx.y;
-    const TileCoord tc = tile_coord(p, tx, lband, lane);
-    const uint32_t tile = lband * tiles_x + tx;
-    // (a lane off the image holds zeros, is never sampled and stores nothing)
-    float4 I = make_float4(0.0f, 0.0f, 0.0f, 0.0f), M = I;
-    if (tc.valid) {
-        I = p.out[tc.idx];
-        M = a.moments[tc.idx];
-    }
-    const uint32_t spp = p.spp;                                   // wgsl:343
-    uint32_t ncand = kCandNone, hxy = 0u;
-    bool scene_read = false;                // the tile's list and seed hashes: on first use
-    bool dirty = false;                     // some frame changed a bit of the tile
-    uint64_t m = 0ull;
-    uint32_t taken = 0u;
-    for (uint32_t f = 0; f < p.frames; ++f) {
-        const bool reset = f == 0u && p.reset_first != 0u;
-        // rt_adaptive_error
-        float d = M.y - M.x * M.x;
-        d = d > 0.0f ? d : 0.0f;
-        const float nn = I.w > 1.0f ? I.w : 1.0f;
-        const float err = M.w >= a.min_history ? d / nn : __builtin_inff();
-        // rt_update_adaptive
-        v3 c = mk(0.0f, 0.0f, 0.0f);
-        uint32_t n = 0u;
-        bool sampled = 0u < spp;                                  // a reset: wgsl:345-350
-        if (!reset) {
-            c = mk(I.x, I.y, I.z);                                // wgsl:339-341
-            n = f2u(I.w);
-            const float lm = (0.2126f * I.x + 0.7152f * I.y) + 0.0722f * I.z;
-            const float thr = a.abs_tolerance2 + a.rel_tolerance2 * (lm * lm);
-            const bool converged = n >= a.min_samples && err <= thr;  // (a NaN: not converged)
-            sampled = n < spp && !converged;
-        }
-        sampled = sampled && tc.valid;
-        m = rt_ballot(sampled);
-        if (m != 0ull) {
-            if (!scene_read) {
-                ncand = (kScan != kTraceExhaustive && p.cand) ? load_cnt(p.cand, tile)
-                                                              : kCandNone;
-                hxy = p.hx[min(tc.x, p.width - 1u)] ^ p.hy[min(tc.y, p.height - 1u)];
-                scene_read = true;
-            }
-            const Cam cam = cam_params(p);
-            const v3 col = sample<kScan>(p, cam, tile, ncand, tc, hxy, n, p.seed_b[f], f, sampled,
-                                         false);
-            if (sampled) {
-                const float k = (float)(n + 1u);                  // wgsl:356
-                c = mk(c.x + (col.x - c.x) / k, c.y + (col.y - c.y) / k, c.z + (col.z - c.z) / k);
-                n += 1u;
-            }
-            taken += (uint32_t)__popcll(m);
-        }
-        const float4 O = make_float4(c.x, c.y, c.z, (float)n);    // wgsl:362-363
-        // rt_moments_update on (I, O): rules 1 and 2 share the running means' step, rule 3 keeps
-        // M and rule 4 zeroes it
-        const bool r1 = O.w == 1.0f;
-        const bool r2 = !r1 && O.w == I.w + 1.0f;
-        float4 N = M;
-        if (!(r1 || r2) && !(O.w == I.w)) N = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (rt_ballot(r1 || r2) != 0ull) {
-            const float sx = r1 ? O.x : I.x + O.w * (O.x - I.x);
-            const float sy = r1 ? O.y : I.y + O.w * (O.y - I.y);
-            const float sz = r1 ? O.z : I.z + O.w * (O.z - I.z);
-            const float k0 = r1 ? 0.0f : M.w;
-            const bool fresh = k0 == 0.0f;
-            const float m1 = fresh ? 0.0f : M.x, m2 = fresh ? 0.0f : M.y;
-            const float L = (0.2126f * sx + 0.7152f * sy) + 0.0722f * sz;
-            const float kk = k0 + 1.0f;
-            const float4 S = make_float4(m1 + (L - m1) / kk, m2 + (L * L - m2) / kk, 0.0f, kk);
-            if (r1 || r2) N = S;
-        }
-        const bool changed =
-            tc.valid &&
-            (((__float_as_uint(O.x) ^ __float_as_uint(I.x)) |
-              (__float_as_uint(O.y) ^ __float_as_uint(I.y)) |
-              (__float_as_uint(O.z) ^ __float_as_uint(I.z)) |
-              (__float_as_uint(O.w) ^ __float_as_uint(I.w)) |
-              (__float_as_uint(N.x) ^ __float_as_uint(M.x)) |
-              (__float_as_uint(N.y) ^ __float_as_uint(M.y)) |
-              (__float_as_uint(N.z) ^ __float_as_uint(M.z)) |
-              (__float_as_uint(N.w) ^ __float_as_uint(M.w))) != 0u);
-        const bool any_changed = rt_ballot(changed) != 0ull;
-        I = O;
-        M = N;
-        dirty = dirty || any_changed;
-        if (!any_changed && m == 0ull && !reset) break;           // a fixed point: see above
-    }
-    // (after an early exit m is 0: the frames left out sample nothing)
-    if (lane == 0u) {
-        if (a.tile_mask) a.tile_mask[tile] = m;
-        if (a.tile_samples) {
-            if (a.first)
-                a.tile_samples[tile] = taken;
-            else if (taken != 0u)
-                a.tile_samples[tile] += taken;
-        }
-    }
-    // a later launch of the call that changes nothing finds the plane its predecessor wrote
-    if (!tc.valid || !(dirty || a.first)) return;
-    if (dirty) {
-        p.out[tc.idx] = I;
-        a.moments[tc.idx] = M;
-    }
-    if (a.error) {
-        float d = M.y - M.x * M.x;
-        d = d > 0.0f ? d : 0.0f;
-        const float nn = I.w > 1.0f ? I.w : 1.0f;
-        a.error[tc.idx] = M.w >= a.min_history ? d / nn : __builtin_inff();
-    }
-}
-
-hipError_t launch_converge(const TraceParams& p, const ConvergeParams& a, int kernel,
-                           hipStream_t stream) {
-    const dim3 grid = tile_grid(p);
-    if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    if (kernel == kTraceList)
-        hipLaunchKernelGGL(rt_converge_kernel<kTraceList>, grid, dim3(256), 0, stream, p, a);
-    else if (kernel == kTraceCulled)
-        hipLaunchKernelGGL(rt_converge_kernel<kTraceCulled>, grid, dim3(256), 0, stream, p, a);
-    else if (kernel == kTraceExhaustive)
-        hipLaunchKernelGGL(rt_converge_kernel<kTraceExhaustive>, grid, dim3(256), 0, stream, p,
-                           a);
-    else
-        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

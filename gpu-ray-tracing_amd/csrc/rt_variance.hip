@@ -3,21 +3,15 @@
 // translation unit of its own: the render's kernels (rt_kernels.hip), the denoiser's
 // (rt_denoise.hip) and the reprojection's (rt_reproject.hip) are not recompiled with it.
 //
-// Every float operation below is the one the header names, in its order: the build has
-// -ffp-contract=off, IEEE division and subnormals on, so the output is bit-identical to the
-// NumPy restatements in tests/test_variance.py.
+// Every float operation below is the one the header names, in its order (the rules shared with
+// the sampler: rt_pixel_rules.h): the build has -ffp-contract=off, IEEE division and
+// subnormals on, so the output is bit-identical to the NumPy restatements in
+// tests/test_variance.py.
 #include "rt_atrous.h"
+#include "rt_pixel_rules.h"
 #include "rt_variance_kernels.h"
 
 namespace rtk {
-
-namespace {
-
-__device__ __forceinline__ float luminance(float x, float y, float z) {
-    return (0.2126f * x + 0.7152f * y) + 0.0722f * z;
-}
-
-}  // namespace
 
 // One lane per pixel, 16-byte loads and one 16-byte store; consecutive lanes consecutive
 // pixels.  A lane past the image does nothing; a pixel under rule 3 stores nothing.
@@ -35,6 +29,7 @@ __global__ __launch_bounds__(256) void rt_moments_update_kernel(const MomentsPar
         const float4 I = p.in[at];
         if (O.w == I.w + 1.0f) {                                      // rule 2
             const float4 M = p.moments[at];
+            // (recover_sample, written out: see rt_pixel_rules.h)
             sx = I.x + O.w * (O.x - I.x);
             sy = I.y + O.w * (O.y - I.y);
             sz = I.z + O.w * (O.z - I.z);
@@ -49,9 +44,7 @@ __global__ __launch_bounds__(256) void rt_moments_update_kernel(const MomentsPar
             return;
         }
     }
-    const float L = luminance(sx, sy, sz);
-    const float kk = k0 + 1.0f;
-    p.moments[at] = make_float4(m1 + (L - m1) / kk, m2 + (L * L - m2) / kk, 0.0f, kk);
+    p.moments[at] = moments_push(m1, m2, k0, luminance(sx, sy, sz));
 }
 
 hipError_t launch_moments_update(const MomentsParams& p, hipStream_t stream) {
@@ -108,10 +101,7 @@ struct VarianceFilter {
     static __device__ __forceinline__ float load_variance(const Params& p, size_t idx, float n) {
         if (!p.moments) return p.vin[idx];
         const float4 m = p.moments[idx];
-        float d = m.y - m.x * m.x;
-        d = d > 0.0f ? d : 0.0f;
-        const float nn = n > 1.0f ? n : 1.0f;
-        return m.w >= p.min_history ? d / nn : p.fallback;
+        return gated_variance(m.x, m.y, m.w, n, p.min_history, p.fallback);
     }
 
     static __device__ __forceinline__ Texel load(const Params& p, size_t idx) {

@@ -35,7 +35,7 @@ W, H = 37, 21                 # two partial tile columns (37 = 4 * 8 + 5), a par
 PLANES = ("sphere_id", "hit", "normal", "material")
 FLOAT_PLANES = PLANES[1:]
 MISS = -1                     # RT_AOV_MISS as the id plane's int32
-CULL_MIN = 32                 # rt_kernels.hip kCullMinSpheres: the cone route starts here
+CULL_MIN = 32                 # rt_trace_device.h kCullMinSpheres: the cone route starts here
 RT_ERR_INVALID_ARGUMENT = 1
 SENT_F, SENT_I = -12345.0, 0x5A5A5A5A
 TAIL = 16                     # 64 bytes of sentinel after every plane

@@ -746,7 +746,7 @@ def _lattice_scene(rng, jitter=0.9, twins=False, y_spread=0.0):
 @pytest.mark.parametrize("case", ["lattice", "twins", "inside", "down", "tall", "aligned"])
 def test_grid_walk_equals_exhaustive(rt, case):
     """Bounce rays whose wave cone is too wide walk the XZ grid of the small spheres
-    (rt_kernels.hip scan_grid): bitwise equal to the exhaustive scan, for coincident
+    (rt_trace_device.h scan_grid): bitwise equal to the exhaustive scan, for coincident
     spheres (index tie-break), a camera inside the cluster, rays straight down (zero x/z
     direction components), a tall slab and spheres centred on cell boundaries."""
     rng = np.random.default_rng(["lattice", "twins", "inside", "down", "tall",

@@ -1,8 +1,8 @@
 """The shader's own input space at its edges: materials, depth and sphere count.
 
-The shading of a hit exists four times in rt_kernels.hip (shade_hit of the one-frame and chain
-kernels, ray_color<kScan> of the exhaustive, culled and list instances, the tile-pair kernel's
-path, scatter_path of the bounce instances), so every case here runs through every route of its
+The shading of a hit exists four times (rt_kernels.hip: shade_hit of the one-frame and chain
+kernels, the tile-pair kernel's path, scatter_path of the bounce instances; rt_trace_device.h:
+ray_color<kScan> of the exhaustive, culled and list instances), so every case here runs through every route of its
 depth and the kernel name of each launch is asserted (a silent re-routing would show):
 
   depth <= 1   `update` under the four modes of test_gpu_parity's `pipe` fixture;
@@ -698,7 +698,7 @@ C_BACK = [33, 2, 0]                       # the one-context sequence shrinks aga
 C_DEPTHS = [3, 1]
 C_LARGE = [4095, 4096, 4097]
 K_GRID_MIN_SPHERES = 64                   # rt_abi.cpp
-K_CULL_MIN_SPHERES = 32                   # rt_kernels.hip: shorter lists are scanned whole
+K_CULL_MIN_SPHERES = 32                   # rt_trace_device.h: shorter lists are scanned whole
 K_LDS_MAX_RECORDS = 4096                  # rt_kernels.h
 
 

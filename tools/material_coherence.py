@@ -1,7 +1,7 @@
 """How much would material-coherent shading save in the one-frame kernel? (CPU, no GPU.)
 
 rt_single_kernel<2> gives each lane two pixels — the same position in two horizontally
-adjacent 8x8 tiles (rt_kernels.hip tile_coord, single_body) — and shades each pixel slot in
+adjacent 8x8 tiles (rt_trace_device.h tile_coord, rt_kernels.hip single_body) — and shades each pixel slot in
 turn (shade_hit): the Lambertian arithmetic on every lane, then the metal and / or dielectric
 branch (wgsl:95-135) for the whole wave whenever any lane of that slot hit such a sphere.
 Three ways to run those branches over a wave's 128 pixels, counted in branch passes per
