@@ -153,6 +153,10 @@ struct rt_ctx {
     uint32_t timed_launches = 0;
     // rt_pick's record on the device: four 16-B slots (id, hit, normal, material)
     float4* d_pick = nullptr;
+    // rt_progress_stats' blocks (rti::progress_blocks): the report and the workgroups' records on
+    // the device, the report's pinned landing place on the host
+    void* d_progress = nullptr;
+    void* h_progress = nullptr;
 };
 
 namespace {
@@ -188,25 +192,66 @@ void forget_count(rt_ctx* ctx, const void* image) {
         }
 }
 
+// The round-robin stripes of rank / nranks as a band set (band b -> rank b mod nranks).
+rt_band_set stripe_set(uint32_t h, uint32_t rank, uint32_t nranks) {
+    const uint32_t bands = (h + RT_STRIPE_ROWS - 1) / RT_STRIPE_ROWS;
+    return {rank, nranks, bands > rank ? (bands - rank + nranks - 1) / nranks : 0u};
+}
+
+// A band set the kernels can run: inside the image, step >= 1, and (for two or more bands)
+// first and step within the packed stripe map's 16 / 15 bits (rtk::pack_bands).
+rt_status check_band_set(uint32_t h, const rt_band_set& bs) {
+    const uint32_t bands = (h + RT_STRIPE_ROWS - 1) / RT_STRIPE_ROWS;
+    if (bs.step == 0) return fail(RT_ERR_INVALID_ARGUMENT, "band set step is 0");
+    if (bs.count == 0) return RT_OK;
+    if (bs.first >= bands || (uint64_t)bs.first + (uint64_t)(bs.count - 1u) * bs.step >= bands)
+        return fail(RT_ERR_INVALID_ARGUMENT, "band set reaches past the image");
+    if (bs.first > 0xFFFFu || (bs.count >= 2u && bs.step >= 0x7FFFu))
+        return fail(RT_ERR_INVALID_ARGUMENT, "band set first / step out of range");
+    return RT_OK;
+}
+
+// What rt_update_adaptive, rt_converge_frames and rt_progress_stats refuse of an
+// rt_adaptive_params.
+rt_status check_adaptive_params(const rt_adaptive_params& params) {
+    if (params.min_samples > (1u << 24))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
+    if (!nonneg_finite(params.abs_tolerance2) || !nonneg_finite(params.rel_tolerance2))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
+    return RT_OK;
+}
+
+rt_status progress_blocks(rt_ctx* ctx, size_t dev_bytes, size_t host_bytes, void** dev,
+                          void** host) {
+    if (!ctx->d_progress) {
+        hipError_t e = hipMalloc(&ctx->d_progress, dev_bytes);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(progress block)");
+    }
+    if (!ctx->h_progress) {
+        hipError_t e = hipHostMalloc(&ctx->h_progress, host_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(progress report)");
+    }
+    *dev = ctx->d_progress;
+    *host = ctx->h_progress;
+    return RT_OK;
+}
+
 }  // namespace rti
 
 namespace {
 
+using rti::check_adaptive_params;
+using rti::check_band_set;
 using rti::check_image;
 using rti::DeviceGuard;
 using rti::fail;
 using rti::forget_count;
 using rti::hip_fail;
+using rti::host_f2u;
+using rti::stripe_set;
 
 constexpr uint32_t kMaxSpheres = 1u << 20;
 constexpr uint32_t kScanPad = 68;  // >= chunk round-up + one chunk + a 64-lane block
-
-// WGSL u32(f32) on the host (truncate, saturate, NaN -> 0), as rtd::f2u.
-uint32_t host_f2u(float f) {
-    if (!(f > 0.0f)) return 0u;
-    if (f >= 4294967296.0f) return 0xFFFFFFFFu;
-    return (uint32_t)f;
-}
 
 double norm3(const float* v) {
     return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
@@ -1092,25 +1137,6 @@ void fill_camera(rtk::TraceParams& p, const rt_scene_camera& c) {
     p.spp = host_f2u(c.samples_per_pixel);
 }
 
-// The round-robin stripes of rank / nranks as a band set (band b -> rank b mod nranks).
-rt_band_set stripe_set(uint32_t h, uint32_t rank, uint32_t nranks) {
-    const uint32_t bands = (h + RT_STRIPE_ROWS - 1) / RT_STRIPE_ROWS;
-    return {rank, nranks, bands > rank ? (bands - rank + nranks - 1) / nranks : 0u};
-}
-
-// A band set the kernels can run: inside the image, step >= 1, and (for two or more bands)
-// first and step within the packed stripe map's 16 / 15 bits (rtk::pack_bands).
-rt_status check_band_set(uint32_t h, const rt_band_set& bs) {
-    const uint32_t bands = (h + RT_STRIPE_ROWS - 1) / RT_STRIPE_ROWS;
-    if (bs.step == 0) return fail(RT_ERR_INVALID_ARGUMENT, "band set step is 0");
-    if (bs.count == 0) return RT_OK;
-    if (bs.first >= bands || (uint64_t)bs.first + (uint64_t)(bs.count - 1u) * bs.step >= bands)
-        return fail(RT_ERR_INVALID_ARGUMENT, "band set reaches past the image");
-    if (bs.first > 0xFFFFu || (bs.count >= 2u && bs.step >= 0x7FFFu))
-        return fail(RT_ERR_INVALID_ARGUMENT, "band set first / step out of range");
-    return RT_OK;
-}
-
 // Common setup of every trace launch: argument checks, scene upload, kernel parameters
 // (camera, stripe map, scan-mode data such as the candidate lists).
 rt_status prepare(rt_ctx* ctx, const void* in, const void* out, uint32_t w, uint32_t h,
@@ -1507,6 +1533,8 @@ rt_status rt_destroy(rt_ctx* ctx) {
         (void)hipFree(ctx->split_cnt);
         (void)hipFree(ctx->unit_order);
         (void)hipFree(ctx->d_pick);
+        (void)hipFree(ctx->d_progress);
+        if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
         free_candidates(ctx);
         for (uint32_t k = 0; k + 1 < RT_MAX_UPDATE_QUEUES; ++k) {
             if (ctx->aux[k]) (void)hipStreamDestroy(ctx->aux[k]);
@@ -1733,15 +1761,6 @@ rt_status rt_pick(rt_ctx* ctx, uint32_t w, uint32_t h, uint32_t x, uint32_t y,
 }  // extern "C"
 
 namespace {
-
-// What rt_update_adaptive and rt_converge_frames refuse of an rt_adaptive_params.
-rt_status check_adaptive_params(const rt_adaptive_params& params) {
-    if (params.min_samples > (1u << 24))
-        return fail(RT_ERR_INVALID_ARGUMENT, "min_samples above 16777216");
-    if (!rti::nonneg_finite(params.abs_tolerance2) || !rti::nonneg_finite(params.rel_tolerance2))
-        return fail(RT_ERR_INVALID_ARGUMENT, "a tolerance is negative, NaN or infinite");
-    return RT_OK;
-}
 
 // The instance of rt_adaptive_kernel / rt_converge_kernel for a prepared launch: the context's
 // as trace_kernel_for chooses it, with ray_color's culled scans in place of the bounce instance

@@ -10,6 +10,8 @@
 
 #include "rt_abi.h"
 
+struct rt_adaptive_params;  // include/rt_adaptive.h
+
 namespace rti {
 
 // Records `msg` as this thread's rt_last_error() text and returns `s`.
@@ -24,6 +26,24 @@ int ctx_device(const rt_ctx* ctx);
 // Drops what the context knows about `image`'s sample counts (the source of the kernels' count
 // hint): for a call that leaves per-pixel counts in it.
 void forget_count(rt_ctx* ctx, const void* image);
+// WGSL u32(f32) on the host (truncate, saturate, NaN -> 0), as rtd::f2u.
+inline uint32_t host_f2u(float f) {
+    if (!(f > 0.0f)) return 0u;
+    if (f >= 4294967296.0f) return 0xFFFFFFFFu;
+    return (uint32_t)f;
+}
+// The round-robin stripes of rank / nranks as a band set (band b -> rank b mod nranks).
+rt_band_set stripe_set(uint32_t h, uint32_t rank, uint32_t nranks);
+// A band set the kernels can run: inside the image, step >= 1, and (for two or more bands)
+// first and step within the packed stripe map's 16 / 15 bits (rtk::pack_bands).
+rt_status check_band_set(uint32_t h, const rt_band_set& bs);
+// What rt_update_adaptive, rt_converge_frames and rt_progress_stats refuse of an
+// rt_adaptive_params.
+rt_status check_adaptive_params(const rt_adaptive_params& params);
+// The context's blocks of rt_progress_stats, allocated on first use (the device must be
+// current): dev_bytes on the device, host_bytes of pinned host memory.
+rt_status progress_blocks(rt_ctx* ctx, size_t dev_bytes, size_t host_bytes, void** dev,
+                          void** host);
 // Whether nranks band sets cover every band of a height-row image exactly once, each within
 // rows_per_rank rows (rt_deinterleave_bands' precondition).
 bool band_sets_cover(uint32_t height, uint32_t nranks, const rt_band_set* sets,

@@ -1,20 +1,26 @@
 // rt_post.cpp — C-ABI entry points of the post-processing stages (include/rt_denoise.h,
-// rt_reproject.h, rt_variance.h, rt_adaptive.h's rt_adaptive_error): argument checks and kernel
-// launches.  Of the context they use the device; rt_reproject also drops dst's sample-count
-// record.  (rt_update_adaptive is a trace launch and lives in rt_abi.cpp.)
+// rt_reproject.h, rt_variance.h, rt_adaptive.h's rt_adaptive_error, rt_progress.h): argument
+// checks and kernel launches.  Of the context they use the device; rt_reproject also drops dst's
+// sample-count record, and rt_progress_stats uses the context's report blocks.
+// (rt_update_adaptive and rt_converge_frames are trace launches and live in rt_abi.cpp;
+// rt_progress_run calls rt_converge_frames through its public symbol.)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
 #include "rt_adaptive.h"
 #include "rt_adaptive_kernels.h"
+#include "rt_converge.h"
 #include "rt_denoise.h"
 #include "rt_denoise_kernels.h"
 #include "rt_internal.h"
+#include "rt_progress.h"
+#include "rt_progress_kernels.h"
 #include "rt_reproject.h"
 #include "rt_reproject_kernels.h"
 #include "rt_variance.h"
@@ -44,6 +50,81 @@ rtk::AtrousRoute route_for(uint32_t i, bool direct) {
 // The last of n iterations writes the final buffers, so iteration i writes them when the number
 // of iterations after it is even and the scratch buffers when it is odd.
 bool writes_final(uint32_t n, uint32_t i) { return (n - 1u - i) % 2u == 0u; }
+
+// The report's layout is the kernels' record.
+static_assert(sizeof(rt_progress_report) == sizeof(rtk::ProgressRecord) &&
+                  offsetof(rt_progress_report, samples) ==
+                      offsetof(rtk::ProgressRecord, count) + rtk::kProgSamples * 8 &&
+                  offsetof(rt_progress_report, active_tiles) ==
+                      offsetof(rtk::ProgressRecord, count) + rtk::kProgActiveTiles * 8 &&
+                  offsetof(rt_progress_report, min_count) ==
+                      offsetof(rtk::ProgressRecord, min_count) &&
+                  offsetof(rt_progress_report, max_error) ==
+                      offsetof(rtk::ProgressRecord, max_error),
+              "rt_progress_report and rtk::ProgressRecord differ");
+
+// The argument checks rt_progress_stats and rt_progress_run share.
+rt_status check_progress(const float* image, const float* moments, const float* error,
+                         const uint64_t* tile_active, uint32_t w, uint32_t h,
+                         const rt_adaptive_params* params, uint32_t min_history,
+                         const rt_progress_report* out) {
+    if (!image || !params || !out)
+        return fail(RT_ERR_INVALID_ARGUMENT, "NULL image, params or out_report");
+    if ((moments != nullptr) == (error != nullptr))
+        return fail(RT_ERR_INVALID_ARGUMENT, "exactly one of moments and error is given");
+    const void* const mask = tile_active;
+    if (mask && (mask == image || mask == moments || mask == error))
+        return fail(RT_ERR_INVALID_ARGUMENT, "tile_active is image, moments or error");
+    if (rt_status s = rti::check_adaptive_params(*params)) return s;
+    if (moments && (min_history < 1u || min_history > (1u << 24)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
+    return check_image(w, h);
+}
+
+// Shared body of rt_progress_stats / rt_progress_stats_bands after the checks: the two launches
+// (rt_progress.hip), the report's copy to the context's pinned block and the wait for it.
+rt_status progress_stats(rt_ctx* ctx, const float* image, const float* moments,
+                         const float* error, uint64_t* tile_active, uint32_t w, uint32_t h,
+                         const rt_band_set& bs, uint32_t spp, const rt_adaptive_params& params,
+                         uint32_t min_history, void* stream_v, rt_progress_report* out) {
+    if (bs.count == 0u) {                                 // no pixels: nothing to launch
+        std::memset(out, 0, sizeof(*out));
+        out->min_count = 0xFFFFFFFFu;
+        out->max_error = -HUGE_VALF;
+        return RT_OK;
+    }
+    DeviceGuard guard(ctx_device(ctx));
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    void *dev = nullptr, *host = nullptr;
+    if (rt_status s = rti::progress_blocks(ctx, rtk::kProgressBlockBytes,
+                                           sizeof(rt_progress_report), &dev, &host))
+        return s;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    rtk::ProgressParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.image = reinterpret_cast<const float4*>(image);
+    p.moments = reinterpret_cast<const float4*>(moments);
+    p.error = error;
+    p.tile_active = tile_active;
+    p.block = static_cast<rtk::ProgressRecord*>(dev);
+    p.width = w;
+    p.height = h;
+    p.band_first = bs.first;
+    p.band_step = bs.step;
+    p.local_bands = bs.count;
+    p.spp = spp;
+    p.min_samples = params.min_samples;
+    p.abs_tolerance2 = params.abs_tolerance2;
+    p.rel_tolerance2 = params.rel_tolerance2;
+    p.min_history = (float)min_history;
+    hipError_t e = rtk::launch_progress(p, stream);
+    if (e != hipSuccess) return hip_fail(e, "rt_progress_kernel launch");
+    e = hipMemcpyAsync(host, dev, sizeof(rt_progress_report), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "rt_progress_stats read-back");
+    std::memcpy(out, host, sizeof(*out));
+    return RT_OK;
+}
 
 }  // namespace
 
@@ -324,6 +405,82 @@ rt_status rt_adaptive_error(rt_ctx* ctx, const float* image, const float* moment
     p.min_history = (float)min_history;
     hipError_t e = rtk::launch_adaptive_error(p, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "rt_adaptive_error_kernel launch");
+    return RT_OK;
+}
+
+rt_status rt_progress_stats_bands(rt_ctx* ctx, const float* image, const float* moments,
+                                  const float* error, uint64_t* tile_active, uint32_t w,
+                                  uint32_t h, const rt_band_set* bands, uint32_t spp,
+                                  const rt_adaptive_params* params, uint32_t min_history,
+                                  void* stream, rt_progress_report* out) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!bands) return fail(RT_ERR_INVALID_ARGUMENT, "bands is NULL");
+    if (rt_status s = check_progress(image, moments, error, tile_active, w, h, params,
+                                     min_history, out))
+        return s;
+    if (rt_status s = rti::check_band_set(h, *bands)) return s;
+    return progress_stats(ctx, image, moments, error, tile_active, w, h, *bands, spp, *params,
+                          min_history, stream, out);
+}
+
+rt_status rt_progress_stats(rt_ctx* ctx, const float* image, const float* moments,
+                            const float* error, uint64_t* tile_active, uint32_t w, uint32_t h,
+                            uint32_t spp, const rt_adaptive_params* params, uint32_t min_history,
+                            void* stream, rt_progress_report* out) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (rt_status s = check_progress(image, moments, error, tile_active, w, h, params,
+                                     min_history, out))
+        return s;
+    return progress_stats(ctx, image, moments, error, tile_active, w, h,
+                          rti::stripe_set(h, 0, 1), spp, *params, min_history, stream, out);
+}
+
+// rt_progress.h's loop: reports through progress_stats, frames through rt_converge_frames.
+rt_status rt_progress_run(rt_ctx* ctx, float* image, float* moments, uint64_t* tile_active,
+                          uint32_t w, uint32_t h, const rt_scene_camera* cam,
+                          const rt_sphere* spheres, uint32_t count, const float* seeds,
+                          const rt_adaptive_params* params, uint32_t min_history,
+                          const rt_progress_goal* goal, void* stream, uint32_t* frames_run,
+                          rt_progress_report* out) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!moments || !cam || !seeds || !goal || !frames_run)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "NULL moments, camera, random_seeds, goal or frames_run");
+    if (image == moments) return fail(RT_ERR_INVALID_ARGUMENT, "image is moments");
+    if (goal->max_frames < 1u || goal->max_frames > 65536u || goal->check_every < 1u ||
+        goal->check_every > 65536u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "max_frames or check_every outside 1..65536");
+    if (rt_status s = check_progress(image, moments, nullptr, tile_active, w, h, params,
+                                     min_history, out))
+        return s;
+    const rt_band_set all = rti::stripe_set(h, 0, 1);
+    const uint32_t spp = rti::host_f2u(cam->samples_per_pixel);
+    rt_progress_report report;
+    auto stats = [&]() {
+        return progress_stats(ctx, image, moments, nullptr, tile_active, w, h, all, spp, *params,
+                              min_history, stream, &report);
+    };
+    uint32_t done = 0;
+    const bool moved = cam->camera_has_moved > 0.5f;
+    bool more = true;
+    if (!moved) {
+        if (rt_status s = stats()) return s;
+        more = report.active > goal->max_active;
+    }
+    rt_scene_camera still = *cam;
+    still.camera_has_moved = 0.0f;
+    while (more) {
+        const uint32_t f = std::min(goal->check_every, goal->max_frames - done);
+        if (rt_status s = rt_converge_frames(ctx, image, moments, nullptr, nullptr, nullptr, w, h,
+                                             done == 0u ? cam : &still, spheres, count, f,
+                                             seeds + done, params, min_history, stream))
+            return s;
+        done += f;
+        if (rt_status s = stats()) return s;
+        more = report.active > goal->max_active && done < goal->max_frames;
+    }
+    *frames_run = done;
+    *out = report;
     return RT_OK;
 }
 

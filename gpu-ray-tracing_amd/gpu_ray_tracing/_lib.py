@@ -254,6 +254,29 @@ _SIGS_CONVERGE = {
 RT_CONVERGE_MAX_FRAMES_PER_LAUNCH = 64
 
 
+# include/rt_progress.h (convergence reports and render-to-tolerance)
+_SIGS_PROGRESS = {
+    "rt_progress_stats": (ctypes.c_int, [P, P, P, P, P, U32, U32, U32, P, U32, P, P]),
+    "rt_progress_stats_bands": (ctypes.c_int, [P, P, P, P, P, U32, U32, P, U32, P, U32, P, P]),
+    "rt_progress_run": (ctypes.c_int, [P, P, P, P, U32, U32, P, P, U32, P, P, U32, P, P, P, P]),
+}
+
+
+class ProgressReportC(ctypes.Structure):
+    """rt_progress_report (rt_progress.h), 96 bytes."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("active", ctypes.c_uint64),
+                ("converged", ctypes.c_uint64), ("capped", ctypes.c_uint64),
+                ("below_min", ctypes.c_uint64), ("no_history", ctypes.c_uint64),
+                ("nonfinite", ctypes.c_uint64), ("samples", ctypes.c_uint64),
+                ("active_tiles", ctypes.c_uint64), ("min_count", U32), ("max_count", U32),
+                ("max_error", F), ("_reserved", U32 * 3)]
+
+
+class ProgressGoalC(ctypes.Structure):
+    """rt_progress_goal (rt_progress.h), 16 bytes."""
+    _fields_ = [("max_active", ctypes.c_uint64), ("max_frames", U32), ("check_every", U32)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -299,7 +322,8 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(str(path))
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
-                                  **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE}.items():
+                                  **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
+                                  **_SIGS_PROGRESS}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -370,6 +394,10 @@ def adaptive_symbols() -> list[str]:
 
 def converge_symbols() -> list[str]:
     return list(_SIGS_CONVERGE)
+
+
+def progress_symbols() -> list[str]:
+    return list(_SIGS_PROGRESS)
 
 
 def check(status: int, func: str) -> None:

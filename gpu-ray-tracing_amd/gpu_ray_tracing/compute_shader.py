@@ -848,6 +848,92 @@ class ComputeShaderPipeline:
             _lib.call("rt_converge_frames_bands", *head, _lib.band_sets([bands]), *tail)
         return err, mask, taken
 
+    # ---- convergence reports and render-to-tolerance (rt_progress.h) ---------------------
+    @staticmethod
+    def _report_dict(r) -> dict:
+        return {name: getattr(r, name) for name, _ in _lib.ProgressReportC._fields_
+                if name != "_reserved"}
+
+    def progress_report(self, image: torch.Tensor, width: int, height: int, spp: int, *,
+                        moments: torch.Tensor | None = None, error: torch.Tensor | None = None,
+                        min_samples: int = ADAPTIVE_DEFAULTS["min_samples"],
+                        abs_tolerance2: float = ADAPTIVE_DEFAULTS["abs_tolerance2"],
+                        rel_tolerance2: float = ADAPTIVE_DEFAULTS["rel_tolerance2"],
+                        min_history: int = 4, tile_active=False, bands=None):
+        """rt_progress_stats / rt_progress_stats_bands: every pixel of `image` classified as
+        update_adaptive and converge decide it for these parameters, a samples_per_pixel of `spp`
+        and a camera that has not moved, from `moments` (adaptive_error's estimate) or from an
+        `error` plane, exactly one of the two.  Returns (report, mask): the report a dict of
+        rt_progress_report's fields (pixels, active, converged, capped, below_min, no_history,
+        nonfinite, samples, active_tiles, min_count, max_count, max_error), the mask
+        (tile_active: True, or an int64 tensor of one word per 8 x 8 tile; else None) the active
+        pixels in update_adaptive's tile_mask layout.  bands = (first, step, count): compact
+        local buffers, as update_adaptive.  The call runs on torch's current stream and waits
+        for it: the report is on the host when it returns."""
+        rows = height if bands is None else int(bands[2]) * RT_STRIPE_ROWS
+        _check_image(image, width, rows, "image")
+        if (moments is None) == (error is None):
+            raise ValueError("exactly one of moments and error is given")
+        if moments is not None:
+            _check_image(moments, width, rows, "moments")
+        else:
+            _check_plane(error, width * rows, torch.float32, "error")
+        tiles = ((width + 7) // 8) * ((rows + 7) // 8)
+        mask = None
+        if tile_active is True:
+            mask = torch.empty((tiles,), dtype=torch.int64, device=self.torch_device)
+        elif tile_active is not False and tile_active is not None:
+            mask = _check_plane(tile_active, tiles, torch.int64, "tile_active")
+        params = _lib.AdaptiveParamsC(int(min_samples), float(abs_tolerance2),
+                                      float(rel_tolerance2))
+        report = _lib.ProgressReportC()
+        head = (self._ctx, _ptr(image), _ptr(moments) if moments is not None else None,
+                _ptr(error) if error is not None else None,
+                _ptr(mask) if mask is not None else None, width, height)
+        tail = (int(spp), ctypes.byref(params), int(min_history), self._stream(),
+                ctypes.byref(report))
+        if bands is None:
+            _lib.call("rt_progress_stats", *head, *tail)
+        else:
+            _lib.call("rt_progress_stats_bands", *head, _lib.band_sets([bands]), *tail)
+        return self._report_dict(report), mask
+
+    def render_to_tolerance(self, image: torch.Tensor, moments: torch.Tensor, width: int,
+                            height: int, camera: SceneCamera, spheres: SphereCollection, seeds,
+                            *, max_active: int = 0, check_every: int = 16,
+                            min_samples: int = ADAPTIVE_DEFAULTS["min_samples"],
+                            abs_tolerance2: float = ADAPTIVE_DEFAULTS["abs_tolerance2"],
+                            rel_tolerance2: float = ADAPTIVE_DEFAULTS["rel_tolerance2"],
+                            min_history: int = 4, tile_active=False):
+        """rt_progress_run: `converge` on `image` and `moments` in calls of check_every frames,
+        with a progress_report after each, until at most max_active pixels are active or
+        len(seeds) frames have run.  A camera that has not moved is looked at first, and nothing
+        runs when it is already there; a camera that has moved runs its first call unseen (its
+        frame 0 is a reset).  Returns (frames_run, report, mask) with the last report and its
+        mask as progress_report returns them; `image` and `moments` hold what one `converge` of
+        frames_run frames leaves.  Runs on torch's current stream and waits for it."""
+        _check_image(image, width, height, "image")
+        _check_image(moments, width, height, "moments")
+        tiles = ((width + 7) // 8) * ((height + 7) // 8)
+        mask = None
+        if tile_active is True:
+            mask = torch.empty((tiles,), dtype=torch.int64, device=self.torch_device)
+        elif tile_active is not False and tile_active is not None:
+            mask = _check_plane(tile_active, tiles, torch.int64, "tile_active")
+        s = np.ascontiguousarray(seeds, np.float32)
+        params = _lib.AdaptiveParamsC(int(min_samples), float(abs_tolerance2),
+                                      float(rel_tolerance2))
+        goal = _lib.ProgressGoalC(int(max_active), s.size, int(check_every))
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        report = _lib.ProgressReportC()
+        done = ctypes.c_uint32(0)
+        _lib.call("rt_progress_run", self._ctx, _ptr(image), _ptr(moments),
+                  _ptr(mask) if mask is not None else None, width, height, ctypes.byref(cam), p,
+                  n, _np_ptr(s), ctypes.byref(params), int(min_history), ctypes.byref(goal),
+                  self._stream(), ctypes.byref(done), ctypes.byref(report))
+        return int(done.value), self._report_dict(report), mask
+
     def present(self, image: torch.Tensor, width: int, height: int,
                 encoding: str = "srgb", out: torch.Tensor | None = None) -> torch.Tensor:
         """8-bit RGBA of a float image (rt_present_rgba8), a (H, W, 4) uint8 device tensor:
