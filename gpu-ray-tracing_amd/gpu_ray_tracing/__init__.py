@@ -8,9 +8,9 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (ADAPTIVE_DEFAULTS, DENOISE_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
+from .compute_shader import (ADAPTIVE_DEFAULTS, DENOISE_DEFAULTS, EDIT_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
                              ComputeShaderImages, ComputeShaderNode,
-                             ComputeShaderPipeline, chain_schedule, partition_bands,
+                             ComputeShaderPipeline, chain_schedule, edit_plan, partition_bands,
                              reproject_basis, srgb_thresholds,
                              stripe_band_set, stripe_local_rows)
 from .scene import (SCENE_DEFAULT, SCENE_N, SCENE_THREE, SphereCollection,
@@ -25,6 +25,10 @@ RT_AOV_MISS = _lib.RT_AOV_MISS
 RT_DENOISE_MAX_ITERATIONS = _lib.RT_DENOISE_MAX_ITERATIONS
 # moments and the variance-guided filter (include/rt_variance.h)
 RT_VARIANCE_MAX_ITERATIONS = _lib.RT_VARIANCE_MAX_ITERATIONS
+# scene edits (include/rt_scene_edit.h): edit_plan and ComputeShaderPipeline.carry_edit
+RT_EDIT_NONE = _lib.RT_EDIT_NONE
+RT_EDIT_MOVED = _lib.RT_EDIT_MOVED
+RT_EDIT_MAX_BALLS = _lib.RT_EDIT_MAX_BALLS
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
@@ -34,4 +38,5 @@ __all__ = [
     "partition_bands", "chain_schedule", "stripe_band_set", "AOV_PLANES", "RT_AOV_MISS",
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
     "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS", "ADAPTIVE_DEFAULTS",
+    "EDIT_DEFAULTS", "edit_plan", "RT_EDIT_NONE", "RT_EDIT_MOVED", "RT_EDIT_MAX_BALLS",
 ]

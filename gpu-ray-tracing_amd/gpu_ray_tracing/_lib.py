@@ -277,6 +277,41 @@ class ProgressGoalC(ctypes.Structure):
     _fields_ = [("max_active", ctypes.c_uint64), ("max_frames", U32), ("check_every", U32)]
 
 
+# include/rt_scene_edit.h (carrying the accumulator across scene edits)
+_SIGS_EDIT = {
+    "rt_edit_params_default": (None, [P]),
+    "rt_edit_plan_bytes": (ctypes.c_size_t, [U32]),
+    "rt_edit_plan": (ctypes.c_int, [P, U32, P, U32, P, P, P, ctypes.c_size_t, P]),
+    "rt_edit_carry": (ctypes.c_int, [P, P, P, U32, U32, P, P, P, U32, U32, P, P]),
+}
+RT_EDIT_NONE = 0xFFFFFFFF
+RT_EDIT_MOVED = 0x80000000
+RT_EDIT_MAX_BALLS = 32
+RT_EDIT_MAX_SPHERES = 1 << 20
+
+
+class EditRecordC(ctypes.Structure):
+    """rt_edit_record (rt_scene_edit.h), 32 bytes."""
+    _fields_ = [("prev_center", F * 3), ("scale", F), ("center", F * 3), ("link", U32)]
+
+
+class EditBallC(ctypes.Structure):
+    """rt_edit_ball (rt_scene_edit.h), 32 bytes."""
+    _fields_ = [("center", F * 3), ("radius2", F), ("owner", U32), ("_pad", U32 * 3)]
+
+
+class EditParamsC(ctypes.Structure):
+    """rt_edit_params (rt_scene_edit.h), 32 bytes."""
+    _fields_ = [("carry", ReprojectParamsC), ("edit_history", U32), ("influence", F),
+                ("_reserved", U32 * 2)]
+
+
+class EditInfoC(ctypes.Structure):
+    """rt_edit_info (rt_scene_edit.h), 32 bytes."""
+    _fields_ = [("n_records", U32), ("n_balls", U32), ("n_changed", U32), ("n_moved", U32),
+                ("n_restart", U32), ("n_deleted", U32), ("full_restart", U32), ("_reserved", U32)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -323,7 +358,7 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
-                                  **_SIGS_PROGRESS}.items():
+                                  **_SIGS_PROGRESS, **_SIGS_EDIT}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -398,6 +433,10 @@ def converge_symbols() -> list[str]:
 
 def progress_symbols() -> list[str]:
     return list(_SIGS_PROGRESS)
+
+
+def edit_symbols() -> list[str]:
+    return list(_SIGS_EDIT)
 
 
 def check(status: int, func: str) -> None:

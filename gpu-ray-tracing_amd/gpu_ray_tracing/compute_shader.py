@@ -53,6 +53,56 @@ def reproject_basis(camera: SceneCamera) -> np.ndarray:
     return out.reshape(3, 3)
 
 
+# edit_plan's and ComputeShaderPipeline.carry_edit's defaults: rt_edit_params_default's (the two
+# numbers come from the CPU prototype DESIGN.md 4.13 reports)
+EDIT_DEFAULTS = {"edit_history": 4, "influence": 3.0}
+
+
+def _edit_params(max_history, lambertian_only, position_tolerance2, edit_history, influence):
+    p = _lib.EditParamsC()
+    p.carry = _lib.ReprojectParamsC(int(max_history), 1 if lambertian_only else 0,
+                                    float(position_tolerance2), 0)
+    p.edit_history = int(edit_history)
+    p.influence = float(influence)
+    return p
+
+
+def _sphere_rows(spheres) -> np.ndarray:
+    arr = spheres.spheres if isinstance(spheres, SphereCollection) else spheres
+    arr = np.ascontiguousarray(arr, np.float32)
+    if arr.size % 8:
+        raise ValueError("sphere records are 8 float32 each")
+    return arr.reshape(-1, 8)
+
+
+def edit_plan(prev_spheres, spheres, prev_index=None, *,
+              influence: float = EDIT_DEFAULTS["influence"],
+              edit_history: int = EDIT_DEFAULTS["edit_history"],
+              max_history: int = REPROJECT_DEFAULTS["max_history"]) -> tuple[np.ndarray, dict]:
+    """rt_edit_plan (rt_scene_edit.h): compares the previous scene with the current one
+    (SphereCollections or (n, 8) float32 arrays) and returns (table, info) for
+    ComputeShaderPipeline.carry_edit.  prev_index[i] is the index current sphere i had in the
+    previous scene, RT_EDIT_NONE for a new one; None is the identity.  `table` is a
+    (n_cur + 32, 8) uint32 array of 32-byte rows: info["n_records"] records, then
+    info["n_balls"] balls, the rest zeros.  Host only; raises RtError for what the header
+    refuses."""
+    prev, cur = _sphere_rows(prev_spheres), _sphere_rows(spheres)
+    index = None
+    if prev_index is not None:
+        index = np.ascontiguousarray(np.asarray(prev_index, np.int64).astype(np.uint32))
+        if index.shape != (cur.shape[0],):
+            raise ValueError("prev_index holds one entry per current sphere")
+    table = np.zeros((cur.shape[0] + _lib.RT_EDIT_MAX_BALLS, 8), np.uint32)
+    info = _lib.EditInfoC()
+    params = _edit_params(max_history, True, REPROJECT_DEFAULTS["position_tolerance2"],
+                          edit_history, influence)
+    _lib.call("rt_edit_plan", _np_ptr(prev), prev.shape[0], _np_ptr(cur), cur.shape[0],
+              _np_ptr(index) if index is not None else None, ctypes.byref(params),
+              _np_ptr(table), table.nbytes, ctypes.byref(info))
+    return table, {f: int(getattr(info, f)) for f, _ in _lib.EditInfoC._fields_
+                   if not f.startswith("_")}
+
+
 def inv_sigma2(sigma: float) -> float:
     """1 / sigma^2 in float32, as denoise passes a sigma to rt_denoise (inf for sigma 0,
     which the library refuses; 0 for an infinite sigma: that weight term is off)."""
@@ -656,6 +706,79 @@ class ComputeShaderPipeline:
         cam = prev_camera.to_c()
         _lib.call("rt_reproject", self._ctx, _ptr(prev_image), _ptr(out), width, height,
                   ctypes.byref(cam), ctypes.byref(c), ctypes.byref(params), self._stream())
+        return out
+
+    # ---- carrying across scene edits (rt_scene_edit.h) -----------------------------------
+    def carry_edit(self, prev_image: torch.Tensor, width: int, height: int,
+                   prev_camera: SceneCamera, prev_guides: dict, guides: dict, plan, *,
+                   max_history: int = REPROJECT_DEFAULTS["max_history"],
+                   position_tolerance2: float = REPROJECT_DEFAULTS["position_tolerance2"],
+                   lambertian_only: bool = REPROJECT_DEFAULTS["lambertian_only"],
+                   edit_history: int = EDIT_DEFAULTS["edit_history"],
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+        """rt_edit_carry: `reproject` across an edit of the scene.  prev_guides are trace_aov's
+        planes for the previous scene and camera, guides those for the current scene and
+        camera; `plan` is what edit_plan returned for the two scenes, (table, info), where
+        `table` may also be a contiguous device tensor that already holds the table's bytes.
+        A host table is copied to the device on torch's current stream, so the call touches no
+        scene state of the pipeline.  A sphere that moved or was resized carries its own
+        surface's history; pixels inside the plan's balls keep at most edit_history samples
+        (0: they restart); recoloured and new spheres restart.  Every bit of `out` (allocated
+        when not given; returned) equals the NumPy restatement in tests/test_scene_edit.py.
+        Enqueued on torch's current stream."""
+        need = width * height * 4
+
+        def image_like(t, what, dtype=torch.float32, n=need):
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) {dtype} tensor of at "
+                                 f"least {n} elements")
+            return t
+
+        image_like(prev_image, "prev_image")
+        names = ("sphere_id", "hit", "normal") + (("material",) if lambertian_only else ())
+        missing = [f"prev_guides[{k!r}]" for k in ("sphere_id", "hit")
+                   if prev_guides.get(k) is None]
+        missing += [f"guides[{k!r}]" for k in names if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"missing {missing} (the planes of trace_aov)")
+        c = _lib.ReprojectPlanesC()
+        for field, src, k in [("prev_sphere_id", prev_guides, "sphere_id"),
+                              ("prev_hit", prev_guides, "hit")] + \
+                             [(k, guides, k) for k in names]:
+            is_id = k == "sphere_id"
+            what = ("prev_guides" if src is prev_guides else "guides") + f"[{k!r}]"
+            t = image_like(src[k], what, torch.int32 if is_id else torch.float32,
+                           width * height if is_id else need)
+            setattr(c, field, t.data_ptr())
+        try:
+            table, info = plan
+            n_records, n_balls = int(info["n_records"]), int(info["n_balls"])
+        except (TypeError, ValueError, KeyError):
+            raise ValueError("plan is the (table, info) pair of edit_plan") from None
+        rows = n_records + n_balls
+        if isinstance(table, np.ndarray):
+            if table.nbytes < 32 * rows:
+                raise ValueError(f"plan's table holds {table.nbytes} bytes, need {32 * rows}")
+            host = np.ascontiguousarray(table).reshape(-1).view(np.uint8)[:32 * rows]
+            table_dev = torch.from_numpy(host.copy()).to(self.torch_device) if rows else None
+        else:
+            if (not isinstance(table, torch.Tensor) or table.device.type != "cuda"
+                    or not table.is_contiguous()
+                    or table.numel() * table.element_size() < 32 * rows):
+                raise ValueError("plan's table must be a NumPy array or a contiguous CUDA (HIP) "
+                                 f"tensor of at least {32 * rows} bytes")
+            table_dev = table if rows else None
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=self.torch_device)
+        image_like(out, "out")
+        params = _edit_params(max_history, lambertian_only, position_tolerance2, edit_history,
+                              EDIT_DEFAULTS["influence"])
+        cam = prev_camera.to_c()
+        _lib.call("rt_edit_carry", self._ctx, _ptr(prev_image), _ptr(out), width, height,
+                  ctypes.byref(cam), ctypes.byref(c),
+                  _ptr(table_dev) if table_dev is not None else None, n_records, n_balls,
+                  ctypes.byref(params), self._stream())
         return out
 
     # ---- moments and the variance-guided filter (rt_variance.h) --------------------------

@@ -14,9 +14,9 @@ extern "C" {
 #endif
 
 /* Both views have the same width and height and the same scene: the sphere records are unchanged
- * between them (moving spheres are out of scope: a sphere that moved keeps its id and would carry
- * history it should not).  The current camera is not an argument: the current view's hit points
- * are already in world space.
+ * between them (a sphere that moved keeps its id and would carry history it should not here:
+ * rt_scene_edit.h carries the accumulator across an edited scene).  The current camera is not an
+ * argument: the current view's hit points are already in world space.
  *
  * All device arithmetic is f32: every *, + and - is its own IEEE operation (no contraction, no
  * fma), / is correctly rounded, subnormals are kept.  Every output bit equals a CPU restatement
