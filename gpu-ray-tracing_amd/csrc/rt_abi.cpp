@@ -20,6 +20,7 @@
 #include "rt_abi.h"
 #include "rt_aov.h"
 #include "rt_chain_parts.h"
+#include "rt_occlusion_cull.h"
 #include "rt_selftest_roots.h"
 #include "rt_adaptive.h"
 #include "rt_converge.h"
@@ -81,6 +82,9 @@ struct rt_ctx {
     uint64_t cand_live = 0;         // tiles of the current lists
     std::vector<unsigned char> cand_key;
     uint64_t cand_gen = 0;          // bumped whenever the lists are rebuilt
+    // rt_set_occlusion_cull: the list build also drops the entries another entry hides from
+    // every camera ray of the tile (part of cand_key, with the proofs it needs)
+    bool occlusion_cull = true;
     // Cost-ordered tiles (TraceParams::tile_order): per-tile durations recorded by the
     // first camera-ray-only launch of a list generation, and the order derived from them.
     uint32_t* tile_cost = nullptr;
@@ -687,7 +691,7 @@ void free_candidates(rt_ctx* ctx) {
 rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t stream) {
     struct Key {
         float center[3], vul[3], pdu[3], pdv[3], ddu[3], ddv[3], defocus;
-        uint32_t w, h, first, step, bands;
+        uint32_t w, h, first, step, bands, occlusion;
         uint64_t scene;
     } key;
     std::memset(&key, 0, sizeof(key));
@@ -704,6 +708,11 @@ rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t stream
     key.step = p.band_step;
     key.bands = p.local_bands;
     key.scene = ctx->scene_gen;
+    // The occlusion rule bounds the f32 roots, so it runs only inside the domain the fast
+    // cores are proven for (no overflow or underflow in the root test's intermediates).
+    const bool occlusion = ctx->occlusion_cull && ctx->scene_bound <= 0x1p40 &&
+                           camera_rays_bounded(ctx, p);
+    key.occlusion = occlusion ? 1u : 0u;
     const unsigned char* kb = reinterpret_cast<const unsigned char*>(&key);
     const uint64_t tiles = (uint64_t)((p.width + 7u) >> 3) * p.local_bands;
     p.cand_k = rtk::kCandMax;
@@ -722,7 +731,7 @@ rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t stream
             }
             ctx->cand_tiles = tiles;
         }
-        hipError_t e = rtk::launch_candidates(p, ctx->cand, stream);
+        hipError_t e = rtk::launch_candidates(p, ctx->cand, occlusion, stream);
         if (e != hipSuccess) return hip_fail(e, "rt_candidates_kernel launch");
         ctx->cand_key.assign(kb, kb + sizeof(key));
         ctx->cand_gen++;
@@ -1492,6 +1501,36 @@ rt_status rt_candidate_stats(rt_ctx* ctx, uint64_t out[5]) {
             out[2] += c;
             out[3] = std::max<uint64_t>(out[3], c);
         }
+    }
+    return RT_OK;
+}
+
+rt_status rt_set_occlusion_cull(rt_ctx* ctx, int on) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (on != 0 && on != 1) return fail(RT_ERR_INVALID_ARGUMENT, "on must be 0 or 1");
+    ctx->occlusion_cull = on != 0;   // (part of the lists' key: the next trace call rebuilds them)
+    return RT_OK;
+}
+
+rt_status rt_occlusion_cull_stats(rt_ctx* ctx, uint64_t out[2]) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    out[0] = out[1] = 0;
+    if (!ctx->cand || ctx->cand_live == 0) return RT_OK;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    // (count, removed) are the first two words of each tile's kCandStride-float4 block
+    std::vector<uint32_t> head(2 * ctx->cand_live);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy2D(head.data(), 2 * sizeof(uint32_t), ctx->cand,
+                        rtk::kCandStride * sizeof(float4), 2 * sizeof(uint32_t), ctx->cand_live,
+                        hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy2D(candidate counts)");
+    for (uint64_t t = 0; t < ctx->cand_live; ++t) {
+        if (head[2 * t] == rtk::kCandNone) continue;
+        out[0] += head[2 * t + 1];
+        out[1] += head[2 * t + 1] ? 1u : 0u;
     }
     return RT_OK;
 }

@@ -239,8 +239,11 @@ hipError_t launch_deinterleave_bands(const float4* gathered, float4* out, uint32
                                      hipStream_t stream);
 hipError_t launch_init(float4* out, uint64_t texels, hipStream_t stream);
 // Builds the per-tile candidate blocks for p's camera/scene/stripes (p.cand_k entries at
-// most per tile).
-hipError_t launch_candidates(const TraceParams& p, float4* cand, hipStream_t stream);
+// most per tile).  occlusion: also drop the entries another entry of the tile's list hides
+// from every camera ray of the tile (rt_occlusion.h); the caller has established
+// camera_rays_bounded and the scene bound of TraceParams::roots_fast.
+hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion,
+                             hipStream_t stream);
 // wg_order for one-frame launches of `pix` tiles per wave: the workgroups by decreasing
 // candidate-list load (per tile 4 + count for a tile with a list, 64 for a tile without
 // one), sorted by launch_tile_order's buckets;

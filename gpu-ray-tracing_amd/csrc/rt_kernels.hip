@@ -119,6 +119,8 @@ __device__ __forceinline__ void sst_put(int k, unsigned long long t) {
 // with rt_aov.hip, rt_sampler.hip and rt_selftest.hip.  Included after the diagnostic macros
 // above: the header defines the ones left undefined as no-ops.
 #include "rt_trace_device.h"
+// the list build's occlusion rule (rt_candidates_kernel)
+#include "rt_occlusion.h"
 
 namespace rtk {
 
@@ -2010,6 +2012,13 @@ __global__ __launch_bounds__(256) void rt_wg_cost_kernel(const float4* __restric
 // whose cone is degenerate stages every sphere.)  Per tile the cone setup is done once per
 // lane and a sphere costs one cone test, instead of 64 lanes repeating the setup and
 // testing all spheres per tile.
+// occl (rt_set_occlusion_cull, and the host's camera_rays_bounded and scene bound hold): each
+// lane then drops from its finished list the entries that another entry of the list hides
+// from every camera ray of the tile (rt_occlusion.h: the entry with the smallest upper bound
+// on its near root among those every ray certainly hits hides every entry whose lower bound
+// exceeds it), closes the gaps in place (index order kept, each entry's sphere record beside
+// its scan record as before) and leaves the number dropped in the count word's .y (u32 bits;
+// rt_occlusion_cull_stats).  A tile without a list, or whose cone is degenerate, is left alone.
 #ifndef RT_CAND_BX
 #define RT_CAND_BX 8
 #endif
@@ -2022,10 +2031,15 @@ static_assert(kCandBX * kCandBY <= 64, "one lane per tile");
 constexpr uint32_t kCandGroup = 8;                 // blocks of 64 spheres per pass
 constexpr uint32_t kCandStage = 64 * kCandGroup;   // spheres per pass
 __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
-                                                           float4* __restrict__ cand) {
+                                                           float4* __restrict__ cand,
+                                                           const uint32_t occl) {
     __shared__ float4 s_rec[kCandStage];
     __shared__ float4 s_sph[2 * kCandStage];
     __shared__ uint32_t s_idx[kCandStage];
+    // the occlusion pass's copy of each lane's list and of its entries' lower bounds (a lane
+    // reads its own slots only)
+    __shared__ float4 s_own[kCandMax][64];
+    __shared__ float s_lo[kCandMax][64];
     const float4* __restrict__ geom = p.geom;
     const float4* __restrict__ gsph = p.sph;
     const uint32_t count = p.count;
@@ -2047,7 +2061,7 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
     const bool ok = mine && footprint_cone(p, (float)(tx * 8u), (float)(tx * 8u + 8u), row0(lb),
                                            row0(lb) + 8.0f, k);
     const uint32_t tile = lb * tiles_x + tx;
-    const uint32_t K = p.cand_k;
+    const uint32_t K = min(p.cand_k, kCandMax);
     float4* const own = cand + (size_t)tile * kCandStride;
     float4* const rec = own + kCandRecOff;
     float4* const sph = own + kCandSphOff;
@@ -2086,6 +2100,7 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
             if (ok && !cone_misses(k, gj)) {
                 if (n < K) {
                     rec[n] = gj;
+                    s_own[n][lane] = gj;
                     sph[2u * n] = s_sph[2u * j];
                     sph[2u * n + 1u] = s_sph[2u * j + 1u];
                 }
@@ -2095,12 +2110,41 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
         __syncthreads();                                        // (the next group restages)
     }
     if (!mine) return;
+    uint32_t removed = 0;
+    if (occl && ok && n <= K && n >= 2u) {
+        const Lens lens = bundle_lens(p, k);
+        // the occluder: the smallest upper bound among the entries every ray certainly hits
+        float t_occ = __builtin_inff();
+        uint32_t j_occ = kCandNone;
+        for (uint32_t j = 0; j < n; ++j) {
+            const OccBounds b = occ_bounds(k, lens, s_own[j][lane]);
+            s_lo[j][lane] = b.lo;
+            if (b.covers && b.hi < t_occ) {
+                t_occ = b.hi;
+                j_occ = j;
+            }
+        }
+        if (j_occ != kCandNone) {
+            uint32_t m = 0;
+            for (uint32_t j = 0; j < n; ++j) {
+                if (j != j_occ && s_lo[j][lane] > t_occ) continue;   // hidden
+                if (m != j) {
+                    rec[m] = s_own[j][lane];
+                    sph[2u * m] = sph[2u * j];
+                    sph[2u * m + 1u] = sph[2u * j + 1u];
+                }
+                ++m;
+            }
+            removed = n - m;
+            n = m;
+        }
+    }
     const uint32_t c = ok && n <= K ? n : kCandNone;
     // zero the chunk padding after the last record
     if (c != kCandNone)
         for (uint32_t q = n; q < ((n + 3u) & ~3u); ++q)
             rec[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    own[0] = make_float4(__uint_as_float(c), 0.0f, 0.0f, 0.0f);
+    own[0] = make_float4(__uint_as_float(c), __uint_as_float(removed), 0.0f, 0.0f);
 }
 
 __global__ __launch_bounds__(256) void rt_init_kernel(float4* __restrict__ out, uint64_t n) {
@@ -2533,12 +2577,14 @@ hipError_t launch_trace(const TraceParams& p, int kernel, hipStream_t stream) {
     return launch_trace_as<kTraceExhaustive>(p, 0, stream);
 }
 
-hipError_t launch_candidates(const TraceParams& p, float4* cand, hipStream_t stream) {
+hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion,
+                             hipStream_t stream) {
     const uint32_t tiles_x = (p.width + 7u) >> 3;
     const dim3 grid((tiles_x + kCandBX - 1u) / kCandBX,
                     (p.local_bands + kCandBY - 1u) / kCandBY);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    hipLaunchKernelGGL(rt_candidates_kernel, grid, dim3(64), 0, stream, p, cand);
+    hipLaunchKernelGGL(rt_candidates_kernel, grid, dim3(64), 0, stream, p, cand,
+                       occlusion ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -153,6 +153,12 @@ _SIGS_CHAIN_PARTS = {
     "rt_chain_schedule": (ctypes.c_int, [U32, U32, ctypes.c_int, P, U32, ctypes.POINTER(U32)]),
 }
 
+# include/rt_occlusion_cull.h
+_SIGS_OCCLUSION = {
+    "rt_set_occlusion_cull": (ctypes.c_int, [P, ctypes.c_int]),
+    "rt_occlusion_cull_stats": (ctypes.c_int, [P, P]),
+}
+
 # include/rt_selftest_roots.h
 _SIGS_SELFTEST_ROOTS = {
     "rt_selftest_roots": (ctypes.c_int, [P, ctypes.c_uint64, P]),
@@ -358,7 +364,7 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
-                                  **_SIGS_PROGRESS, **_SIGS_EDIT}.items():
+                                  **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -401,6 +407,10 @@ def exported_symbols() -> list[str]:
 
 def chain_parts_symbols() -> list[str]:
     return list(_SIGS_CHAIN_PARTS)
+
+
+def occlusion_symbols() -> list[str]:
+    return list(_SIGS_OCCLUSION)
 
 
 def selftest_roots_symbols() -> list[str]:

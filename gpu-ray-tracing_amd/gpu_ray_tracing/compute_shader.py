@@ -240,6 +240,11 @@ class ComputeShaderPipeline:
         parts wherever the conditions hold); identical pixels."""
         _lib.call("rt_set_chain_parts", self._ctx, int(parts))
 
+    def set_occlusion_cull(self, on: bool) -> None:
+        """rt_set_occlusion_cull: whether the candidate-list build drops the entries another
+        entry hides from every camera ray of the tile (default on); identical pixels."""
+        _lib.call("rt_set_occlusion_cull", self._ctx, 1 if on else 0)
+
     def set_update_submit(self, mode: str) -> None:
         """rt_set_update_submit: how update_frames submits one-frame updates — "auto" (HIP
         launches; AQL is opt-in), "hip" or "aql" (AQL packets on the context's own HSA
@@ -313,10 +318,17 @@ class ComputeShaderPipeline:
         _lib.call("rt_candidate_stats", self._ctx, out)
         t, none, entries, mx, cap = (int(v) for v in out)
         listed = t - none
-        return {"tiles": t, "tiles_without_list": none,
-                "no_list_frac": round(none / t, 6) if t else 0.0,
-                "mean_entries": round(entries / listed, 3) if listed else 0.0,
-                "max_entries": mx, "capacity": cap}
+        stats = {"tiles": t, "tiles_without_list": none,
+                 "no_list_frac": round(none / t, 6) if t else 0.0,
+                 "mean_entries": round(entries / listed, 3) if listed else 0.0,
+                 "max_entries": mx, "capacity": cap}
+        if hasattr(_lib.lib(), "rt_occlusion_cull_stats"):   # (absent from older builds)
+            occ = (ctypes.c_uint64 * 2)()
+            _lib.call("rt_occlusion_cull_stats", self._ctx, occ)
+            stats["entries"] = entries
+            stats["occlusion_removed"] = int(occ[0])
+            stats["occlusion_tiles"] = int(occ[1])
+        return stats
 
     def selftest_fastmath(self, n_random: int = 1 << 26) -> list[int]:
         """rt_selftest_fastmath: [defocus, division, sqrt, root-selection mismatches,
