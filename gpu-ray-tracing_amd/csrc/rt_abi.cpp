@@ -161,6 +161,11 @@ struct rt_ctx {
     // the device, the report's pinned landing place on the host
     void* d_progress = nullptr;
     void* h_progress = nullptr;
+    // rt_matte.h's blocks (rti::matte_blocks): the last call's info words, then the selection
+    // mask of rt_matte_resolve; the words the device mask holds
+    uint32_t* d_matte = nullptr;
+    size_t matte_mask_words = 0;
+    std::vector<uint32_t> matte_mask;
 };
 
 namespace {
@@ -1452,6 +1457,48 @@ rt_status trace_aov(rt_ctx* ctx, const rt_aov_planes* planes, uint32_t w, uint32
 
 }  // namespace
 
+namespace rti {
+
+rt_status scene_records(rt_ctx* ctx, const rt_sphere* spheres, uint32_t count, hipStream_t stream,
+                        const float4** geom) {
+    if (rt_status s = upload_spheres(ctx, spheres, count, stream)) return s;
+    *geom = ctx->d_geom;
+    return RT_OK;
+}
+
+int ctx_scan_mode(const rt_ctx* ctx) { return ctx->scan_mode; }
+
+rt_status matte_blocks(rt_ctx* ctx, size_t mask_words, MatteBlocks* out) {
+    constexpr size_t kInfoWords = 16;               // rt_matte_info, padded to 64 bytes
+    if (!ctx->d_matte || ctx->matte_mask_words < mask_words) {
+        uint32_t* d = nullptr;
+        hipError_t e = hipMalloc(&d, (kInfoWords + mask_words) * sizeof(uint32_t));
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(matte blocks)");
+        e = hipMemset(d, 0, (kInfoWords + mask_words) * sizeof(uint32_t));
+        if (e == hipSuccess && ctx->d_matte) {
+            // queued launches may still read the old block
+            e = hipDeviceSynchronize();
+            if (e == hipSuccess)
+                e = hipMemcpy(d, ctx->d_matte, kInfoWords * sizeof(uint32_t),
+                              hipMemcpyDeviceToDevice);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail(e, "matte blocks setup");
+        }
+        (void)hipFree(ctx->d_matte);
+        ctx->d_matte = d;
+        ctx->matte_mask_words = mask_words;
+        ctx->matte_mask.clear();                    // the new mask holds zeros
+    }
+    out->info = ctx->d_matte;
+    out->mask = ctx->d_matte + kInfoWords;
+    out->mask_host = &ctx->matte_mask;
+    return RT_OK;
+}
+
+}  // namespace rti
+
 extern "C" {
 
 uint32_t rt_abi_version(void) { return RT_ABI_VERSION; }
@@ -1573,6 +1620,7 @@ rt_status rt_destroy(rt_ctx* ctx) {
         (void)hipFree(ctx->unit_order);
         (void)hipFree(ctx->d_pick);
         (void)hipFree(ctx->d_progress);
+        (void)hipFree(ctx->d_matte);
         if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
         free_candidates(ctx);
         for (uint32_t k = 0; k + 1 < RT_MAX_UPDATE_QUEUES; ++k) {

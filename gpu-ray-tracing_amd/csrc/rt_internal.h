@@ -1,5 +1,5 @@
 // rt_internal.h — helpers shared by the C-ABI translation units of librt_hip.so
-// (rt_abi.cpp, rt_post.cpp, rt_comm.cpp, rt_chain.cpp).  Internal; not part of the public
+// (rt_abi.cpp, rt_post.cpp, rt_scene_edit.cpp, rt_matte.cpp, rt_comm.cpp, rt_chain.cpp).  Internal; not part of the public
 // boundary.
 #pragma once
 
@@ -7,6 +7,7 @@
 
 #include <cfloat>
 #include <string>
+#include <vector>
 
 #include "rt_abi.h"
 
@@ -44,6 +45,22 @@ rt_status check_adaptive_params(const rt_adaptive_params& params);
 // current): dev_bytes on the device, host_bytes of pinned host memory.
 rt_status progress_blocks(rt_ctx* ctx, size_t dev_bytes, size_t host_bytes, void** dev,
                           void** host);
+// The context's scene for an entry point outside rt_abi.cpp: uploads the spheres as every trace
+// call does (only when their bytes change; the device must be current) and returns the scan
+// records (cx, cy, cz, r*r), zero-padded as the scans expect.  Nothing else of the context changes.
+rt_status scene_records(rt_ctx* ctx, const rt_sphere* spheres, uint32_t count, hipStream_t stream,
+                        const float4** geom);
+// rt_set_scan_mode's value.
+int ctx_scan_mode(const rt_ctx* ctx);
+// The context's blocks of rt_matte.h, allocated on first use (the device must be current): the
+// last call's rt_matte_info on the device, rt_matte_resolve's selection mask (mask_words words)
+// and the host copy of the words the device mask holds.
+struct MatteBlocks {
+    uint32_t* info;
+    uint32_t* mask;
+    std::vector<uint32_t>* mask_host;
+};
+rt_status matte_blocks(rt_ctx* ctx, size_t mask_words, MatteBlocks* out);
 // Whether nranks band sets cover every band of a height-row image exactly once, each within
 // rows_per_rank rows (rt_deinterleave_bands' precondition).
 bool band_sets_cover(uint32_t height, uint32_t nranks, const rt_band_set* sets,

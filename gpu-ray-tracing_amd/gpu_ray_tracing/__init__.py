@@ -29,6 +29,8 @@ RT_VARIANCE_MAX_ITERATIONS = _lib.RT_VARIANCE_MAX_ITERATIONS
 RT_EDIT_NONE = _lib.RT_EDIT_NONE
 RT_EDIT_MOVED = _lib.RT_EDIT_MOVED
 RT_EDIT_MAX_BALLS = _lib.RT_EDIT_MAX_BALLS
+# coverage mattes (include/rt_matte.h): ComputeShaderPipeline.new_matte / matte_frames / matte_resolve
+RT_MATTE_SLOTS = _lib.RT_MATTE_SLOTS
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
@@ -39,4 +41,5 @@ __all__ = [
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
     "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS", "ADAPTIVE_DEFAULTS",
     "EDIT_DEFAULTS", "edit_plan", "RT_EDIT_NONE", "RT_EDIT_MOVED", "RT_EDIT_MAX_BALLS",
+    "RT_MATTE_SLOTS",
 ]

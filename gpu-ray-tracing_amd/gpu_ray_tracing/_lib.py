@@ -318,6 +318,30 @@ class EditInfoC(ctypes.Structure):
                 ("n_restart", U32), ("n_deleted", U32), ("full_restart", U32), ("_reserved", U32)]
 
 
+# include/rt_matte.h (sample-coverage ID mattes)
+_SIGS_MATTE = {
+    "rt_matte_frames": (ctypes.c_int, [P, P, U32, U32, P, P, U32, P, U32, P]),
+    "rt_matte_frames_bands": (ctypes.c_int, [P, P, U32, U32, P, P, P, U32, P, U32, P]),
+    "rt_matte_resolve": (ctypes.c_int, [P, P, ctypes.c_uint64, P, U32, P, P, P]),
+    "rt_matte_last_info": (ctypes.c_int, [P, P]),
+}
+RT_MATTE_SLOTS = 4
+RT_MATTE_MAX_FRAMES = 65536
+RT_MATTE_LIST_CAPACITY = 64
+MATTE_PLANES = ("ids", "counts", "tally")
+
+
+class MattePlanesC(ctypes.Structure):
+    """rt_matte_planes (rt_matte.h): device pointers, 24 bytes."""
+    _fields_ = [("ids", P), ("counts", P), ("tally", P)]
+
+
+class MatteInfoC(ctypes.Structure):
+    """rt_matte_info (rt_matte.h), 16 bytes."""
+    _fields_ = [("list_tiles", U32), ("fallback_tiles", U32), ("longest_list", U32),
+                ("overflow_tiles", U32)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -364,7 +388,8 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**_SIGS, **_SIGS_CHAIN_PARTS, **_SIGS_SELFTEST_ROOTS,
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
-                                  **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION}.items():
+                                  **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION,
+                                  **_SIGS_MATTE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -447,6 +472,10 @@ def progress_symbols() -> list[str]:
 
 def edit_symbols() -> list[str]:
     return list(_SIGS_EDIT)
+
+
+def matte_symbols() -> list[str]:
+    return list(_SIGS_MATTE)
 
 
 def check(status: int, func: str) -> None:

@@ -617,6 +617,99 @@ class ComputeShaderPipeline:
                 "p": np.array(r.p, np.float32), "normal": np.array(r.normal, np.float32),
                 "front_face": bool(r.front_face), "color": np.array(r.color, np.float32)}
 
+    # ---- sample-coverage ID mattes (rt_matte.h) ------------------------------------------
+    def new_matte(self, width: int, height: int) -> dict[str, torch.Tensor]:
+        """The empty matte state of a width x height image (or of a band buffer of `height`
+        rows): "ids" and "counts" ((H, W, 4) int32, the u32 words of rt_matte.h; the background id
+        RT_AOV_MISS reads -1, as trace_aov's sphere_id plane) and "tally" ((H, W, 2) int32:
+        samples taken, samples that found no slot)."""
+        return {"ids": torch.zeros((height, width, 4), dtype=torch.int32, device=self.torch_device),
+                "counts": torch.zeros((height, width, 4), dtype=torch.int32,
+                                      device=self.torch_device),
+                "tally": torch.zeros((height, width, 2), dtype=torch.int32,
+                                     device=self.torch_device)}
+
+    @staticmethod
+    def _matte_planes(matte: dict, pixels: int) -> "_lib.MattePlanesC":
+        c = _lib.MattePlanesC()
+        for name in _lib.MATTE_PLANES:
+            t = matte.get(name) if isinstance(matte, dict) else None
+            if t is None:
+                raise ValueError(f"matte[{name!r}] is missing (the planes of new_matte)")
+            _check_plane(t, pixels * (2 if name == "tally" else 4), torch.int32,
+                         f"matte[{name!r}]")
+            setattr(c, name, t.data_ptr())
+        return c
+
+    def matte_frames(self, matte: dict, width: int, height: int, camera: SceneCamera,
+                     spheres: SphereCollection, seeds) -> dict:
+        """rt_matte_frames: len(seeds) frames of first-hit counting over the planes of
+        new_matte, in place (returned).  Frame f traces, per pixel, the camera ray `update`
+        traces for that pixel's sample count and seeds[f] — jitter and lens included — and
+        counts the sphere it hits first (the background as RT_AOV_MISS) in the pixel's four
+        slots.  Frame 0 honours camera.camera_has_moved (a reset).  Enqueued on torch's current
+        stream."""
+        c = self._matte_planes(matte, width * height)
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        s = np.ascontiguousarray(seeds, np.float32)
+        _lib.call("rt_matte_frames", self._ctx, ctypes.byref(c), width, height,
+                  ctypes.byref(cam), p, n, _np_ptr(s), s.size, self._stream())
+        return matte
+
+    def matte_frames_bands(self, matte: dict, width: int, height: int, bands,
+                           camera: SceneCamera, spheres: SphereCollection, seeds) -> dict:
+        """rt_matte_frames_bands: matte_frames over the band set bands = (first, step, count);
+        the planes are compact local buffers of count * 8 rows with global pixel coordinates,
+        as update_frames_bands."""
+        c = self._matte_planes(matte, width * int(bands[2]) * RT_STRIPE_ROWS)
+        cam = camera.to_c()
+        p, n = self._spheres(spheres)
+        s = np.ascontiguousarray(seeds, np.float32)
+        _lib.call("rt_matte_frames_bands", self._ctx, ctypes.byref(c), width, height,
+                  _lib.band_sets([bands]), ctypes.byref(cam), p, n, _np_ptr(s), s.size,
+                  self._stream())
+        return matte
+
+    def matte_resolve(self, matte: dict, selected, *, alpha: bool = True,
+                      dominant: bool = False, out: dict | None = None) -> dict:
+        """rt_matte_resolve over every pixel the planes hold (a whole image or a band buffer).
+        selected: sphere indices (below 2^20) and / or RT_AOV_MISS (-1 is accepted) for the
+        background.  Returns {"alpha": (H, W) float32 — the fraction of the pixel's samples
+        that saw a selected id, 0 where no sample was taken} and / or {"dominant": (H, W) int32
+        — the id of the fullest slot, -1 (RT_AOV_MISS) where no sample was taken}.  Buffers
+        come from `out` where given."""
+        t = matte.get("tally") if isinstance(matte, dict) else None
+        if not isinstance(t, torch.Tensor) or t.numel() % 2:
+            raise ValueError("matte['tally'] is missing (the planes of new_matte)")
+        pixels = t.numel() // 2
+        shape = tuple(t.shape[:-1]) if t.dim() > 1 else (pixels,)
+        c = self._matte_planes(matte, pixels)
+        sel = np.ascontiguousarray(np.asarray(selected, np.int64).reshape(-1) & 0xFFFFFFFF,
+                                   np.uint32)
+        res = {}
+        for name, want, dtype in (("alpha", alpha, torch.float32),
+                                  ("dominant", dominant, torch.int32)):
+            if not want:
+                continue
+            buf = out.get(name) if out else None
+            if buf is None:
+                buf = torch.empty(shape, dtype=dtype, device=self.torch_device)
+            res[name] = _check_plane(buf, pixels, dtype, f"out[{name!r}]")
+        _lib.call("rt_matte_resolve", self._ctx, ctypes.byref(c), pixels,
+                  _np_ptr(sel) if sel.size else None, sel.size,
+                  _ptr(res["alpha"]) if "alpha" in res else None,
+                  _ptr(res["dominant"]) if "dominant" in res else None, self._stream())
+        return res
+
+    def matte_info(self) -> dict:
+        """rt_matte_last_info: how the last matte_frames call found its first hits — tiles that
+        walked their own sphere list, tiles that fell back to the per-frame scan (and how many
+        of those because the list overflowed), the longest list."""
+        r = _lib.MatteInfoC()
+        _lib.call("rt_matte_last_info", self._ctx, ctypes.byref(r))
+        return {k: int(getattr(r, k)) for k, _ in _lib.MatteInfoC._fields_}
+
     # ---- the denoiser (rt_denoise.h) -----------------------------------------------------
     def denoise(self, image: torch.Tensor, width: int, height: int, guides: dict, *,
                 iterations: int = DENOISE_DEFAULTS["iterations"],
