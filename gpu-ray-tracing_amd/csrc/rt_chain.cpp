@@ -1,5 +1,5 @@
 // rt_chain.cpp — one-frame `update` dispatches submitted as AQL packets on HSA queues the
-// context owns (rt_set_update_submit; AUTO uses it for mid-sized rank shares, rt_abi.cpp
+// context owns (rt_set_update_submit; AUTO uses it for mid-sized rank shares, rt_frames.cpp
 // usable_chain): the per-frame dispatch loop of ComputeShaderNode::run (lib.rs:366-374,
 // 408-417) with a host cost of a packet write per frame instead of a HIP launch.
 //

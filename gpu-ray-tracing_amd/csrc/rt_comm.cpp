@@ -90,7 +90,7 @@ rt_status rt_comm_create(rt_ctx* ctx, const uint8_t id[RT_COMM_ID_BYTES], uint32
     if (!id || !out_comm) return fail(RT_ERR_INVALID_ARGUMENT, "NULL id or out_comm");
     *out_comm = nullptr;
     if (nranks == 0 || rank >= nranks) return fail(RT_ERR_INVALID_ARGUMENT, "bad rank/nranks");
-    const int dev = rti::ctx_device(ctx);
+    const int dev = ctx->device;
     DeviceGuard guard(dev);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     rt_comm* c = new (std::nothrow) rt_comm();
@@ -192,7 +192,7 @@ rt_status rt_gather_stripes(rt_ctx* ctx, rt_comm* comm, const float* local, floa
     if (!local) return fail(RT_ERR_INVALID_ARGUMENT, "local is NULL");
     if (rt_status s = rti::check_image(width, height)) return s;
     if (root >= comm->nranks) return fail(RT_ERR_INVALID_ARGUMENT, "root >= nranks");
-    if (rti::ctx_device(ctx) != comm->device)
+    if (ctx->device != comm->device)
         return fail(RT_ERR_INVALID_ARGUMENT, "ctx and comm are on different devices");
     const bool is_root = comm->rank == root;
     if (is_root && !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is NULL on the root");
@@ -229,7 +229,7 @@ rt_status rt_gather_bands(rt_ctx* ctx, rt_comm* comm, const float* local, float*
     if (!local || !sets) return fail(RT_ERR_INVALID_ARGUMENT, "local or sets is NULL");
     if (rt_status s = rti::check_image(width, height)) return s;
     if (root >= comm->nranks) return fail(RT_ERR_INVALID_ARGUMENT, "root >= nranks");
-    if (rti::ctx_device(ctx) != comm->device)
+    if (ctx->device != comm->device)
         return fail(RT_ERR_INVALID_ARGUMENT, "ctx and comm are on different devices");
     const bool is_root = comm->rank == root;
     if (is_root && !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is NULL on the root");

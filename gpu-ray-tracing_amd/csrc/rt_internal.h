@@ -1,6 +1,12 @@
-// rt_internal.h — helpers shared by the C-ABI translation units of librt_hip.so
-// (rt_abi.cpp, rt_post.cpp, rt_scene_edit.cpp, rt_matte.cpp, rt_comm.cpp, rt_chain.cpp).  Internal; not part of the public
-// boundary.
+// rt_internal.h — what the C-ABI translation units of librt_hip.so share: the context
+// (rt_context.h), the error and argument helpers, and what each unit exports to the others.
+//   rt_abi.cpp      errors, argument checks, create / destroy, setters, diagnostics, bands, present
+//   rt_scene.cpp    scene upload, bounce grid, the fast cores' domain
+//   rt_plan.cpp     kernel choice, candidate lists, orders, count records and hints, prepare
+//   rt_frames.cpp   rt_update_frames and the render calls: fork / join, AQL glue, chain schedule
+//   rt_tracers.cpp  the trace launches beside the render: G-buffer, pick, adaptive, converge
+//   rt_post.cpp, rt_scene_edit.cpp, rt_matte.cpp, rt_comm.cpp, rt_chain.cpp
+// Internal; not part of the public boundary.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -10,11 +16,16 @@
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_context.h"
 
 struct rt_adaptive_params;  // include/rt_adaptive.h
+namespace rtk {
+struct TraceParams;         // rt_kernels.h
+}
 
 namespace rti {
 
+// ---- rt_abi.cpp ----
 // Records `msg` as this thread's rt_last_error() text and returns `s`.
 rt_status fail(rt_status s, const std::string& msg);
 rt_status hip_fail(hipError_t e, const char* what);
@@ -22,17 +33,37 @@ rt_status hip_fail(hipError_t e, const char* what);
 rt_status check_image(uint32_t w, uint32_t h);
 // Whether a parameter is neither negative, NaN nor infinite.
 inline bool nonneg_finite(float x) { return x >= 0.0f && x <= FLT_MAX; }
-// The HIP device of a context (rt_create's argument).
-int ctx_device(const rt_ctx* ctx);
-// Drops what the context knows about `image`'s sample counts (the source of the kernels' count
-// hint): for a call that leaves per-pixel counts in it.
-void forget_count(rt_ctx* ctx, const void* image);
 // WGSL u32(f32) on the host (truncate, saturate, NaN -> 0), as rtd::f2u.
 inline uint32_t host_f2u(float f) {
     if (!(f > 0.0f)) return 0u;
     if (f >= 4294967296.0f) return 0xFFFFFFFFu;
     return (uint32_t)f;
 }
+// The seed words of a launch's n frames (wgsl:311: u32(random_seed * 2^32)).
+inline void fill_seeds(uint32_t* seed_b, const float* seeds, uint32_t n) {
+    for (uint32_t f = 0; f < n; ++f) seed_b[f] = host_f2u(seeds[f] * 4294967296.0f);
+}
+// The camera's ray grid, and its lens, in a kernel parameter block (TraceParams, AovParams,
+// MatteParams).
+template <class P>
+void fill_camera_grid(P& p, const rt_scene_camera& c) {
+    for (int i = 0; i < 3; ++i) {
+        p.center[i] = c.center[i];
+        p.vul[i] = c.viewport_upper_left[i];
+        p.pdu[i] = c.pixel_delta_u[i];
+        p.pdv[i] = c.pixel_delta_v[i];
+    }
+}
+template <class P>
+void fill_camera_lens(P& p, const rt_scene_camera& c) {
+    for (int i = 0; i < 3; ++i) {
+        p.ddu[i] = c.defocus_disk_u[i];
+        p.ddv[i] = c.defocus_disk_v[i];
+    }
+    p.defocus_angle = c.defocus_angle;
+}
+// The 8x8 tiles of a launch over b bands of a w-texel-wide image.
+inline uint64_t launch_tiles(uint32_t w, uint32_t b) { return (uint64_t)((w + 7u) >> 3) * b; }
 // The round-robin stripes of rank / nranks as a band set (band b -> rank b mod nranks).
 rt_band_set stripe_set(uint32_t h, uint32_t rank, uint32_t nranks);
 // A band set the kernels can run: inside the image, step >= 1, and (for two or more bands)
@@ -41,30 +72,54 @@ rt_status check_band_set(uint32_t h, const rt_band_set& bs);
 // What rt_update_adaptive, rt_converge_frames and rt_progress_stats refuse of an
 // rt_adaptive_params.
 rt_status check_adaptive_params(const rt_adaptive_params& params);
-// The context's blocks of rt_progress_stats, allocated on first use (the device must be
-// current): dev_bytes on the device, host_bytes of pinned host memory.
-rt_status progress_blocks(rt_ctx* ctx, size_t dev_bytes, size_t host_bytes, void** dev,
-                          void** host);
-// The context's scene for an entry point outside rt_abi.cpp: uploads the spheres as every trace
-// call does (only when their bytes change; the device must be current) and returns the scan
-// records (cx, cy, cz, r*r), zero-padded as the scans expect.  Nothing else of the context changes.
-rt_status scene_records(rt_ctx* ctx, const rt_sphere* spheres, uint32_t count, hipStream_t stream,
-                        const float4** geom);
-// rt_set_scan_mode's value.
-int ctx_scan_mode(const rt_ctx* ctx);
-// The context's blocks of rt_matte.h, allocated on first use (the device must be current): the
-// last call's rt_matte_info on the device, rt_matte_resolve's selection mask (mask_words words)
-// and the host copy of the words the device mask holds.
-struct MatteBlocks {
-    uint32_t* info;
-    uint32_t* mask;
-    std::vector<uint32_t>* mask_host;
-};
-rt_status matte_blocks(rt_ctx* ctx, size_t mask_words, MatteBlocks* out);
 // Whether nranks band sets cover every band of a height-row image exactly once, each within
 // rows_per_rank rows (rt_deinterleave_bands' precondition).
 bool band_sets_cover(uint32_t height, uint32_t nranks, const rt_band_set* sets,
                      uint32_t rows_per_rank);
+
+// ---- rt_scene.cpp ----
+bool camera_rays_bounded(const rt_ctx* ctx, const rtk::TraceParams& p);
+// The scene upload every trace call does (only when the bytes change; the device must be
+// current): afterwards ctx->d_geom holds the scan records (cx, cy, cz, r*r), zero-padded as the
+// scans expect, and ctx->d_sph the sphere records.  Nothing outside the scene fields changes.
+rt_status upload_spheres(rt_ctx* ctx, const rt_sphere* spheres, uint32_t count,
+                         hipStream_t stream);
+
+// ---- rt_plan.cpp ----
+int trace_kernel_for(const rt_ctx* ctx, const rtk::TraceParams& p);
+int single_or(const rt_ctx* ctx, const rtk::TraceParams& p, int kernel);
+uint32_t frames_per_launch_for(const rt_ctx* ctx, const rtk::TraceParams& p);
+int frame_group_kernel(const rt_ctx* ctx, const rtk::TraceParams& p);
+// The scheduling units of a frame-group kernel's launch: tiles per unit, units per band row, units.
+struct UnitGrid {
+    uint32_t group, units_x;
+    uint64_t units;
+};
+UnitGrid frame_group_units(int kernel, uint32_t w, uint32_t bands);
+uint32_t update_parts(const rt_ctx* ctx, const rtk::TraceParams& p, int kernel);
+uint32_t update_parts_aql(const rt_ctx* ctx, const rtk::TraceParams& p);
+void free_candidates(rt_ctx* ctx);
+rt_status ensure_order_buffers(rt_ctx* ctx, uint64_t tiles, hipStream_t stream);
+rt_status plan_tile_order(rt_ctx* ctx, rtk::TraceParams& p, int kernel, hipStream_t stream);
+rt_status plan_wg_order(rt_ctx* ctx, rtk::TraceParams& p, int kernel, hipStream_t stream);
+rt_status plan_hint_rs(rt_ctx* ctx, rtk::TraceParams& p, int kernel);
+rt_status plan_split(rt_ctx* ctx, rtk::TraceParams& p, int kernel, hipStream_t stream);
+void finish_tile_order(rt_ctx* ctx, const rtk::TraceParams& p);
+bool lookup_count(const rt_ctx* ctx, const void* image, const rtk::TraceParams& p, uint32_t& n);
+void record_count(rt_ctx* ctx, const void* image, const rtk::TraceParams& p, uint32_t n);
+// Drops what the context knows about `image`'s sample counts (the source of the kernels' count
+// hint): for a call that leaves per-pixel counts in it.
+void forget_count(rt_ctx* ctx, const void* image);
+uint32_t next_count(uint32_t n, uint32_t spp);
+uint32_t fill_hint(rtk::TraceParams& p, uint32_t n_in);
+void plan_hint(rt_ctx* ctx, rtk::TraceParams& p, const void* in, const void* out);
+void fill_camera(rtk::TraceParams& p, const rt_scene_camera& c);
+rt_status prepare(rt_ctx* ctx, const void* in, const void* out, uint32_t w, uint32_t h,
+                  const rt_band_set& bs, const rt_scene_camera* cam, const rt_sphere* spheres,
+                  uint32_t count, const float* seeds, hipStream_t stream, rtk::TraceParams& p);
+
+// ---- rt_frames.cpp ----
+rt_status chain_report(rt_ctx* ctx);
 
 // Switches to a device for the duration of a call.
 struct DeviceGuard {
@@ -81,10 +136,6 @@ struct DeviceGuard {
 };
 
 }  // namespace rti
-
-namespace rtk {
-struct TraceParams;
-}
 
 // One-frame updates as AQL packets on context-owned HSA queues (rt_chain.cpp).  A segment
 // is begin, up to kMaxSegmentPackets frame packets (one per frame and part, part k on queue

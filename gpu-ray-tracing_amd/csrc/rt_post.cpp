@@ -2,7 +2,7 @@
 // rt_reproject.h, rt_variance.h, rt_adaptive.h's rt_adaptive_error, rt_progress.h): argument
 // checks and kernel launches.  Of the context they use the device; rt_reproject also drops dst's
 // sample-count record, and rt_progress_stats uses the context's report blocks.
-// (rt_update_adaptive and rt_converge_frames are trace launches and live in rt_abi.cpp;
+// (rt_update_adaptive and rt_converge_frames are trace launches and live in rt_tracers.cpp;
 // rt_progress_run calls rt_converge_frames through its public symbol.)
 #include <hip/hip_runtime_api.h>
 
@@ -29,7 +29,6 @@
 namespace {
 
 using rti::check_image;
-using rti::ctx_device;
 using rti::DeviceGuard;
 using rti::fail;
 using rti::hip_fail;
@@ -81,6 +80,21 @@ rt_status check_progress(const float* image, const float* moments, const float* 
     return check_image(w, h);
 }
 
+// The context's blocks of rt_progress_stats, allocated on first use (the device must be
+// current): rtk::kProgressBlockBytes on the device, the report in pinned host memory.
+rt_status progress_blocks(rt_ctx* ctx) {
+    if (!ctx->d_progress) {
+        hipError_t e = hipMalloc(&ctx->d_progress, rtk::kProgressBlockBytes);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(progress block)");
+    }
+    if (!ctx->h_progress) {
+        hipError_t e = hipHostMalloc(&ctx->h_progress, sizeof(rt_progress_report),
+                                     hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(progress report)");
+    }
+    return RT_OK;
+}
+
 // Shared body of rt_progress_stats / rt_progress_stats_bands after the checks: the two launches
 // (rt_progress.hip), the report's copy to the context's pinned block and the wait for it.
 rt_status progress_stats(rt_ctx* ctx, const float* image, const float* moments,
@@ -93,12 +107,10 @@ rt_status progress_stats(rt_ctx* ctx, const float* image, const float* moments,
         out->max_error = -HUGE_VALF;
         return RT_OK;
     }
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
-    void *dev = nullptr, *host = nullptr;
-    if (rt_status s = rti::progress_blocks(ctx, rtk::kProgressBlockBytes,
-                                           sizeof(rt_progress_report), &dev, &host))
-        return s;
+    if (rt_status s = progress_blocks(ctx)) return s;
+    void *const dev = ctx->d_progress, *const host = ctx->h_progress;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     rtk::ProgressParams p;
     std::memset(&p, 0, sizeof(p));
@@ -157,7 +169,7 @@ rt_status rt_denoise(rt_ctx* ctx, const float* src, float* dst, float* scratch, 
     if (n >= 2u && (!scratch || scratch == src || scratch == dst))
         return fail(RT_ERR_INVALID_ARGUMENT, "iterations >= 2 need a scratch image of their own");
     if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     const bool direct = direct_forced();
     rtk::DenoiseParams p;
@@ -253,7 +265,7 @@ rt_status rt_reproject(rt_ctx* ctx, const float* prev, float* dst, uint32_t w, u
     std::memset(&p, 0, sizeof(p));
     float rows[9];
     if (rt_status s = rt_reproject_basis(prev_camera, rows)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     p.prev = reinterpret_cast<const float4*>(prev);
     p.dst = reinterpret_cast<float4*>(dst);
@@ -299,7 +311,7 @@ rt_status rt_moments_update(rt_ctx* ctx, const float* in, const float* out, floa
     if (in == out || moments == in || moments == out)
         return fail(RT_ERR_INVALID_ARGUMENT, "two of in_rgba, out_rgba and moments are equal");
     if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     rtk::MomentsParams p;
     p.in = reinterpret_cast<const float4*>(in);
@@ -351,7 +363,7 @@ rt_status rt_variance_filter(rt_ctx* ctx, const float* src, float* dst, float* s
                         "iterations >= 2 need a variance_scratch plane of their own");
     }
     if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     const bool direct = direct_forced();
     rtk::VarianceParams p;
@@ -394,7 +406,7 @@ rt_status rt_adaptive_error(rt_ctx* ctx, const float* image, const float* moment
     if (min_history < 1u || min_history > (1u << 24))
         return fail(RT_ERR_INVALID_ARGUMENT, "min_history outside 1..16777216");
     if (rt_status s = check_image(w, h)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     rtk::AdaptiveErrorParams p;
     p.image = reinterpret_cast<const float4*>(image);

@@ -14,7 +14,6 @@
 namespace {
 
 using rti::check_image;
-using rti::ctx_device;
 using rti::DeviceGuard;
 using rti::fail;
 using rti::hip_fail;
@@ -184,7 +183,7 @@ rt_status rt_edit_carry(rt_ctx* ctx, const float* prev, float* dst, uint32_t w, 
     if (rt_status s = check_image(w, h)) return s;
     float rows[9];
     if (rt_status s = rt_reproject_basis(prev_camera, rows)) return s;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
     rtk::EditParams p;
     std::memset(&p, 0, sizeof(p));

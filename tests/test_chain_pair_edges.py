@@ -124,7 +124,7 @@ def run(rt, scene, w, h, depth, defocus, frames, pairs, images, rank=0, nranks=1
 def check(rt, oracle, scene, w, h, depth, defocus, frames, pairs, images):
     new, prev, info, stats = run(rt, scene, w, h, depth, defocus, frames, pairs, images)
     assert info["frames"] == frames
-    # (a launch of one frame is the one-frame kernel's in every mode: rt_abi.cpp, nf == 1)
+    # (a launch of one frame is the one-frame kernel's in every mode: rt_frames.cpp, nf == 1)
     assert info["kernel_name"] == KERNELS[pairs] or frames == 1, info
     assert_same(new, oracle_frames(rt, oracle, scene, w, h, depth, defocus, frames))
     if frames >= 2:

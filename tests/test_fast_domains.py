@@ -36,7 +36,7 @@ def above(x):
     return float(np.nextafter(F32(x), F32(np.inf)))
 
 
-# ---- the host's guards, mirrored in double (rt_abi.cpp) ----------------------------------
+# ---- the host's guards, mirrored in double (rt_scene.cpp) ----------------------------------
 def scene_bound(spheres):
     s = np.asarray(spheres, np.float32).reshape(-1, 8).astype(np.float64)
     if not len(s):
@@ -50,7 +50,7 @@ def radii_ok(spheres):
 
 
 def camera_rays_bounded(cam, w, h, spheres):
-    """camera_rays_bounded of rt_abi.cpp from the camera blob: (bounded, dmin^2, dmax^2)."""
+    """camera_rays_bounded of rt_scene.cpp from the camera blob: (bounded, dmin^2, dmax^2)."""
     c = cam.to_c()
     f = lambda v: np.array(list(v), np.float64)
     center, vul = f(c.center), f(c.viewport_upper_left)

@@ -893,7 +893,7 @@ BOUNCE_PATH_KERNEL = {"per_wave": 0, "compact": 1, "pair": 2, "auto": 0, "split"
 # split_part: three chunks for the costliest 30 % of the tiles (the order's first slots), one
 # unit for every other tile; split_lpt: once an order is measured, the unit order with a
 # threshold that splits only the costlier tiles of these small images (alpha 150: tiles above
-# ~1.8 % of the launch's total cost) — rt_abi.cpp plan_split, RT_BOUNCE_SPLIT / RT_SPLIT_FRAC /
+# ~1.8 % of the launch's total cost) — rt_plan.cpp plan_split, RT_BOUNCE_SPLIT / RT_SPLIT_FRAC /
 # RT_SPLIT_ALPHA
 SPLIT_ENV = {"split_part": {"RT_BOUNCE_SPLIT": "3", "RT_SPLIT_FRAC": "0.3"},
              "split_lpt": {"RT_BOUNCE_SPLIT": "2", "RT_SPLIT_ALPHA": "150"}}

@@ -697,7 +697,7 @@ C_COUNTS = [0, 1, 2, 31, 32, 33, 63, 64, 65, 128, 129]
 C_BACK = [33, 2, 0]                       # the one-context sequence shrinks again
 C_DEPTHS = [3, 1]
 C_LARGE = [4095, 4096, 4097]
-K_GRID_MIN_SPHERES = 64                   # rt_abi.cpp
+K_GRID_MIN_SPHERES = 64                   # rt_scene.cpp
 K_CULL_MIN_SPHERES = 32                   # rt_trace_device.h: shorter lists are scanned whole
 K_LDS_MAX_RECORDS = 4096                  # rt_kernels.h
 
@@ -711,7 +711,7 @@ def c_permutation(rt):
 
 
 def grid_rule(spheres):
-    """build_grid's rule (rt_abi.cpp): (a grid is built, the small spheres counted) — at least
+    """build_grid's rule (rt_scene.cpp): (a grid is built, the small spheres counted) — at least
     kGridMinSpheres spheres within the scene bound, of which at least half that many have a
     radius of at most four times the median."""
     s = np.asarray(spheres, np.float64).reshape(-1, 8)
