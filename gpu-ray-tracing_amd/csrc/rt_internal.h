@@ -5,7 +5,7 @@
 //   rt_plan.cpp     kernel choice, candidate lists, orders, count records and hints, prepare
 //   rt_frames.cpp   rt_update_frames and the render calls: fork / join, AQL glue, chain schedule
 //   rt_tracers.cpp  the trace launches beside the render: G-buffer, pick, adaptive, converge
-//   rt_post.cpp, rt_scene_edit.cpp, rt_matte.cpp, rt_comm.cpp, rt_chain.cpp
+//   rt_post.cpp, rt_scene_edit.cpp, rt_matte.cpp, rt_query.cpp, rt_comm.cpp, rt_chain.cpp
 // Internal; not part of the public boundary.
 #pragma once
 

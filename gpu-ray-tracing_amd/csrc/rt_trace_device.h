@@ -3,7 +3,8 @@
 //
 // Shared by the units whose kernels trace rays or replay the tracer's arithmetic:
 // rt_kernels.hip (the render kernels), rt_aov.hip (the G-buffer), rt_sampler.hip (the adaptive
-// sampler and its fused rounds) and rt_selftest.hip (the fast-math self-tests).  Everything
+// sampler and its fused rounds), rt_selftest.hip (the fast-math self-tests), rt_matte.hip and
+// rt_query.hip (the ray queries: the scans' t_seed / kOcc / route parameters are theirs).  Everything
 // here is __forceinline__ device code, a template or a constant, so a unit pays only for what
 // its kernels call; static LDS (the bounce kernels' s_bounce) is not here, where it would be
 // charged to every kernel of every unit.
@@ -265,10 +266,25 @@ __device__ __forceinline__ uint32_t load_cnt(const float4* cand, uint32_t tile) 
 
 // kFast: camera rays in the host-proven domain (consider_fast).  kScalar: read the records
 // through the constant address space (below).
-template <int K, bool kFast = false, bool kScalar = true>
+// The ray queries' two additions (rt_query.hip), compiled out of every other caller by their
+// defaults, here and in scan_grid_t / scan_grid / scan_culled below:
+//   t_seed  the running tmax starts at the ray's own bound instead of 3.4e35.  Every root
+//           selection takes the running tmax as it finds it — an earlier, nearer hit leaves the
+//           same kind of value there — so their proofs carry over; with idx = -1 beside it,
+//           consider_any's "root < tmax || si < idx" refuses a root equal to the seed as
+//           consider's "tmax <= root" does.
+//   kOcc    occlusion queries: any acceptance answers the query (a sphere that passes its own
+//           test against the seed is accepted by whichever walk meets it first), so a wave
+//           leaves the scan as soon as no live lane is still without one — in the wave-uniform
+//           walks one ballot per chunk that reached a root test (exhaustive) or per 64 records
+//           (cone), in the per-lane grid walk the lane's own exit.  live: the lanes whose
+//           answer is wanted.
+constexpr float kTmaxShader = 0x1.05ed2ep+118f;   // 3.4e35 (wgsl:266)
+template <int K, bool kFast = false, bool kScalar = true, bool kOcc = false>
 __device__ __forceinline__ Hit scan_exhaustive(const float4* __restrict__ geom, uint32_t count,
-                                               v3 o, v3 d) {
-    float tmax = 0x1.05ed2ep+118f;             // 3.4e35 (wgsl:266)
+                                               v3 o, v3 d, float t_seed = kTmaxShader,
+                                               bool live = true) {
+    float tmax = t_seed;                       // 3.4e35 (wgsl:266) unless a query seeds it
     int idx = -1;
     if (count == 0) return Hit{idx, tmax};
     const float a = dot(d, d);                 // wgsl:184 (ray-invariant)
@@ -295,6 +311,7 @@ __device__ __forceinline__ Hit scan_exhaustive(const float4* __restrict__ geom, 
                     else
                         consider(dd[k], hh[k], a, i + k, tmax, idx);
                 }
+            if (kOcc && rt_ballot(live && idx < 0) == 0ull) break;
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) cur[k] = nxt[k];
@@ -531,11 +548,12 @@ __device__ __forceinline__ GridP grid_params(const P& p) {
 // the compares skip the same way.
 // walk: this lane walks the grid (false: a far ray that misses every small sphere, which only
 // tests the big list; grid_usable).
-template <bool kFast>
-__device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live, bool walk) {
+template <bool kFast, bool kOcc = false>
+__device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live, bool walk,
+                                           float t_seed = kTmaxShader) {
     const float a = dot(d, d);
     const float ya = kFast ? rcp_refined(a) : 0.0f;
-    float tmax = 0x1.05ed2ep+118f;             // 3.4e35 (wgsl:266)
+    float tmax = t_seed;                       // 3.4e35 (wgsl:266) unless a query seeds it
     int idx = -1;
     auto test = [&](float disc, float h, uint32_t i, const uint32_t* items) {
         if (kFast)
@@ -552,7 +570,7 @@ __device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live
         if (live) test(disc, h, i, nullptr);
     }
     BCOUNT(26);
-    if (!live || !walk) return Hit{idx, tmax};
+    if (!live || !walk || (kOcc && idx >= 0)) return Hit{idx, tmax};
     BCOUNT(kFast ? 0 : 14);
     // t range of the ray inside the slab and the grid box (t >= 0)
     const float rx = rcp_refined(d.x), ry = rcp_refined(d.y), rz = rcp_refined(d.z);
@@ -594,6 +612,7 @@ __device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live
             const float disc = discriminant(p.geom[k], o, d, a, h);
             test(disc, h, k, p.items);
         }
+        if (kOcc && idx >= 0) break;
         // A cell entered beyond t1, or beyond the closest hit so far, holds no better hit;
         // slack: the walk's position error (grid_e, as t) and 1e-4 of t.
         const float tn = fminf(tx, tz);
@@ -610,10 +629,12 @@ __device__ __forceinline__ Hit scan_grid_t(const GridP& p, v3 o, v3 d, bool live
     }
     return Hit{idx, tmax};
 }
-__device__ __forceinline__ Hit scan_grid(const GridP& p, v3 o, v3 d, bool live, bool walk) {
+template <bool kOcc = false>
+__device__ __forceinline__ Hit scan_grid(const GridP& p, v3 o, v3 d, bool live, bool walk,
+                                         float t_seed = kTmaxShader) {
     if (roots_fast_wave(p.roots_fast, o, dot(d, d), live))
-        return scan_grid_t<true>(p, o, d, live, walk);
-    return scan_grid_t<false>(p, o, d, live, walk);
+        return scan_grid_t<true, kOcc>(p, o, d, live, walk, t_seed);
+    return scan_grid_t<false, kOcc>(p, o, d, live, walk, t_seed);
 }
 
 // The wave may walk the grid: every live ray finite and within reach of the grid margin.
@@ -644,27 +665,34 @@ __device__ __forceinline__ bool grid_usable(const GridP& p, v3 o, v3 d, bool liv
     return rt_ballot(live && !(fin && (walk || far_miss))) == 0ull;
 }
 
-template <bool kLds>
+// route (the ray queries' counters; null: not wanted): receives the scan the wave took.
+constexpr uint32_t kRouteGrid = 0, kRouteCone = 1, kRouteExhaustive = 2;
+template <bool kLds, bool kOcc = false>
 __device__ __forceinline__ Hit scan_culled(const GridP& gp, const float4* __restrict__ geom,
-                                           uint32_t count, v3 o, v3 d, bool live, bool bounce) {
+                                           uint32_t count, v3 o, v3 d, bool live, bool bounce,
+                                           float t_seed = kTmaxShader, uint32_t* route = nullptr) {
     const float4* recs = kLds ? lds_recs : geom;
     // Bounce rays walk the grid whenever the wave may (measured faster than the cone
     // culling even for coherent specular waves); camera rays of tiles without a candidate
     // list keep the cone, whose rays share a narrow beam.
     bool walk;
-    if (bounce && count >= kCullMinSpheres && grid_usable(gp, o, d, live, walk))
-        return scan_grid(gp, o, d, live, walk);
+    if (bounce && count >= kCullMinSpheres && grid_usable(gp, o, d, live, walk)) {
+        if (route) *route = kRouteGrid;
+        return scan_grid<kOcc>(gp, o, d, live, walk, t_seed);
+    }
     (void)bounce;
     (void)gp;
     Cone k;
     if (count < kCullMinSpheres || !wave_cone(o, d, live, k)) {
         BCOUNT(bounce ? 18 : 20);
-        return scan_exhaustive<RT_SCAN_CHUNK>(geom, count, o, d);
+        if (route) *route = kRouteExhaustive;
+        return scan_exhaustive<RT_SCAN_CHUNK, false, true, kOcc>(geom, count, o, d, t_seed, live);
     }
     BCOUNT(bounce ? 22 : 24);
+    if (route) *route = kRouteCone;
     const uint32_t lane = threadIdx.x & 63u;
     const float a = dot(d, d);
-    float tmax = 0x1.05ed2ep+118f;
+    float tmax = t_seed;
     int idx = -1;
     for (uint32_t base = 0; base < count; base += 64u) {
         const float4 g = recs[base + lane];
@@ -678,6 +706,7 @@ __device__ __forceinline__ Hit scan_culled(const GridP& gp, const float4* __rest
             const float disc = discriminant(gs, o, d, a, h);
             consider(disc, h, a, base + (uint32_t)j, tmax, idx);
         }
+        if (kOcc && rt_ballot(live && idx < 0) == 0ull) break;
     }
     return Hit{idx, tmax};
 }

@@ -31,6 +31,9 @@ RT_EDIT_MOVED = _lib.RT_EDIT_MOVED
 RT_EDIT_MAX_BALLS = _lib.RT_EDIT_MAX_BALLS
 # coverage mattes (include/rt_matte.h): ComputeShaderPipeline.new_matte / matte_frames / matte_resolve
 RT_MATTE_SLOTS = _lib.RT_MATTE_SLOTS
+# ray queries (include/rt_query.h): ComputeShaderPipeline.cast_rays / occluded / cast_ray; the
+# names of cast_rays' route counters, in order
+QUERY_ROUTES = _lib.QUERY_ROUTES
 
 __all__ = [
     "CameraSettings", "SceneCamera", "ComputeShaderPipeline", "ComputeShaderImages",
@@ -41,5 +44,5 @@ __all__ = [
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
     "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS", "ADAPTIVE_DEFAULTS",
     "EDIT_DEFAULTS", "edit_plan", "RT_EDIT_NONE", "RT_EDIT_MOVED", "RT_EDIT_MAX_BALLS",
-    "RT_MATTE_SLOTS",
+    "RT_MATTE_SLOTS", "QUERY_ROUTES",
 ]

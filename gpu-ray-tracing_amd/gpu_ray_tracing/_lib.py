@@ -342,6 +342,26 @@ class MatteInfoC(ctypes.Structure):
                 ("overflow_tiles", U32)]
 
 
+# include/rt_query.h (ray queries: closest hit and occlusion for rays the caller chooses)
+_SIGS_QUERY = {
+    "rt_cast_rays": (ctypes.c_int, [P, P, ctypes.c_uint64, U32, P, P, U32, P, P]),
+    "rt_cast_ray": (ctypes.c_int, [P, P, P, U32, P, P]),
+}
+RT_QUERY_CLOSEST = 0
+RT_QUERY_OCCLUSION = 1
+QUERY_ROUTES = ("grid", "cone", "exhaustive")
+
+
+class RayC(ctypes.Structure):
+    """rt_ray (rt_query.h), 32 bytes."""
+    _fields_ = [("o", F * 3), ("tmax", F), ("d", F * 3), ("_reserved", U32)]
+
+
+class QueryPlanesC(ctypes.Structure):
+    """rt_query_planes (rt_query.h): device pointers, 40 bytes."""
+    _fields_ = [("sphere_id", P), ("hit", P), ("normal", P), ("material", P), ("occluded", P)]
+
+
 class BandSetC(ctypes.Structure):
     """rt_band_set (rt_abi.h, ABI 7): global bands first + j * step, j < count."""
     _fields_ = [("first", U32), ("step", U32), ("count", U32)]
@@ -389,7 +409,7 @@ def lib() -> ctypes.CDLL:
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
                                   **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION,
-                                  **_SIGS_MATTE}.items():
+                                  **_SIGS_MATTE, **_SIGS_QUERY}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -476,6 +496,10 @@ def edit_symbols() -> list[str]:
 
 def matte_symbols() -> list[str]:
     return list(_SIGS_MATTE)
+
+
+def query_symbols() -> list[str]:
+    return list(_SIGS_QUERY)
 
 
 def check(status: int, func: str) -> None:

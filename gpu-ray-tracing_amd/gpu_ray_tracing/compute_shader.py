@@ -617,6 +617,96 @@ class ComputeShaderPipeline:
                 "p": np.array(r.p, np.float32), "normal": np.array(r.normal, np.float32),
                 "front_face": bool(r.front_face), "color": np.array(r.color, np.float32)}
 
+    # ---- ray queries (rt_query.h) ---------------------------------------------------------
+    def _rays(self, rays) -> tuple[torch.Tensor, int]:
+        """The (N, 8) float32 ray records on the device: o, tmax, d, a reserved word."""
+        if isinstance(rays, np.ndarray):
+            arr = np.ascontiguousarray(rays, np.float32)
+            if arr.ndim != 2 or arr.shape[1] != 8:
+                raise ValueError("rays must be (N, 8) float32: o, tmax, d, reserved")
+            # (from_numpy refuses to share a read-only array quietly: copy that one)
+            rays = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(
+                self.torch_device)
+        if (not isinstance(rays, torch.Tensor) or rays.device.type != "cuda"
+                or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2
+                or rays.shape[1] != 8):
+            raise ValueError("rays must be a contiguous (N, 8) float32 CUDA (HIP) tensor or a "
+                             "NumPy array")
+        return rays, int(rays.shape[0])
+
+    def cast_rays(self, rays, spheres: SphereCollection,
+                  planes=("sphere_id", "hit", "normal"), out: dict | None = None,
+                  route_counts: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+        """rt_cast_rays, RT_QUERY_CLOSEST: the closest hit of each ray below its own tmax,
+        bit-identical to the oracle's sphere_hit chained in index order.  rays: a contiguous
+        (N, 8) float32 CUDA tensor (o, tmax, d, a reserved word per row), or a NumPy array that
+        is uploaded.  planes: any non-empty subset of trace_aov's, one element per ray
+        ("sphere_id" (N,) int32, the others (N, 4) float32, the same values and miss records).
+        Buffers come from `out` (by plane name) where given, else they are allocated; a buffer
+        of a plane not in `planes` is not touched.  route_counts: a zeroed int32 CUDA tensor of
+        3 words that receives the waves per route (QUERY_ROUTES).  Enqueued on torch's current
+        stream."""
+        planes = tuple(planes)
+        unknown = [k for k in planes if k not in _lib.AOV_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose from {_lib.AOV_PLANES}")
+        rays, n_rays = self._rays(rays)
+        res: dict[str, torch.Tensor] = {}
+        c = _lib.QueryPlanesC()
+        for name in planes:
+            is_id = name == "sphere_id"
+            dtype = torch.int32 if is_id else torch.float32
+            t = out.get(name) if out else None
+            if t is None:
+                t = torch.empty((n_rays,) if is_id else (n_rays, 4), dtype=dtype,
+                                device=self.torch_device)
+            _check_plane(t, n_rays * (1 if is_id else 4), dtype, f"out[{name!r}]")
+            setattr(c, name, t.data_ptr())
+            res[name] = t
+        self._cast(rays, n_rays, _lib.RT_QUERY_CLOSEST, c, spheres, route_counts)
+        return res
+
+    def occluded(self, rays, spheres: SphereCollection, out: torch.Tensor | None = None,
+                 route_counts: torch.Tensor | None = None) -> torch.Tensor:
+        """rt_cast_rays, RT_QUERY_OCCLUSION: per ray 1 where cast_rays reports a hit below the
+        ray's tmax, else 0 ((N,) int32); the scan stops at the first sphere accepted.  rays,
+        route_counts and the stream as cast_rays."""
+        rays, n_rays = self._rays(rays)
+        if out is None:
+            out = torch.empty((n_rays,), dtype=torch.int32, device=self.torch_device)
+        _check_plane(out, n_rays, torch.int32, "out")
+        c = _lib.QueryPlanesC()
+        c.occluded = out.data_ptr()
+        self._cast(rays, n_rays, _lib.RT_QUERY_OCCLUSION, c, spheres, route_counts)
+        return out
+
+    def _cast(self, rays, n_rays, mode, c, spheres, route_counts) -> None:
+        if route_counts is not None:
+            _check_plane(route_counts, 3, torch.int32, "route_counts")
+        p, n = self._spheres(spheres)
+        _lib.call("rt_cast_rays", self._ctx, _ptr(rays) if n_rays else None, n_rays, mode,
+                  ctypes.byref(c), p, n,
+                  _ptr(route_counts) if route_counts is not None else None, self._stream())
+
+    def cast_ray(self, origin, direction, spheres: SphereCollection,
+                 tmax: float = float("inf")) -> dict | None:
+        """rt_cast_ray: the closest hit of one ray below tmax — the record `pick` returns
+        ({"sphere_id", "t", "p", "normal", "front_face", "color"}), or None for a miss.  One
+        wave is launched; returns once the record is on the host."""
+        ray = _lib.RayC()
+        ray.o = tuple(float(np.float32(v)) for v in origin)
+        ray.d = tuple(float(np.float32(v)) for v in direction)
+        ray.tmax = float(np.float32(tmax))
+        r = _lib.PickResultC()
+        p, n = self._spheres(spheres)
+        _lib.call("rt_cast_ray", self._ctx, ctypes.byref(ray), p, n, self._stream(),
+                  ctypes.byref(r))
+        if r.sphere_id == _lib.RT_AOV_MISS:
+            return None
+        return {"sphere_id": int(r.sphere_id), "t": np.float32(r.t),
+                "p": np.array(r.p, np.float32), "normal": np.array(r.normal, np.float32),
+                "front_face": bool(r.front_face), "color": np.array(r.color, np.float32)}
+
     # ---- sample-coverage ID mattes (rt_matte.h) ------------------------------------------
     def new_matte(self, width: int, height: int) -> dict[str, torch.Tensor]:
         """The empty matte state of a width x height image (or of a band buffer of `height`
