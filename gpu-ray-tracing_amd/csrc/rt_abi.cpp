@@ -21,6 +21,7 @@
 #include "rt_chain_parts.h"
 #include "rt_internal.h"
 #include "rt_kernels.h"
+#include "rt_certain_tiles.h"
 #include "rt_occlusion_cull.h"
 #include "rt_selftest_roots.h"
 
@@ -194,6 +195,41 @@ rt_status rt_occlusion_cull_stats(rt_ctx* ctx, uint64_t out[2]) {
         out[0] += head[2 * t + 1];
         out[1] += head[2 * t + 1] ? 1u : 0u;
     }
+    return RT_OK;
+}
+
+rt_status rt_set_certain_tiles(rt_ctx* ctx, int on) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (on != 0 && on != 1) return fail(RT_ERR_INVALID_ARGUMENT, "on must be 0 or 1");
+    ctx->certain_tiles = on != 0;    // (part of the lists' key: the next trace call rebuilds them)
+    return RT_OK;
+}
+
+rt_status rt_certain_tiles_stats(rt_ctx* ctx, uint64_t out[2]) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    out[0] = out[1] = 0;
+    // (RT_SCAN_EXHAUSTIVE reads no lists: whatever an earlier build left is not in use)
+    if (!ctx->cand || ctx->cand_live == 0 || ctx->scan_mode != RT_SCAN_CULLED) return RT_OK;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    // the flag word is the third word of each tile's kCandStride-float4 block
+    std::vector<uint32_t> flags(ctx->cand_live);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy2D(flags.data(), sizeof(uint32_t),
+                        reinterpret_cast<const uint32_t*>(ctx->cand) + 2,
+                        rtk::kCandStride * sizeof(float4), sizeof(uint32_t), ctx->cand_live,
+                        hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy2D(tile flags)");
+    for (uint32_t f : flags) out[0] += f & rtk::kTileCertain;
+    // the pairs of the last tile-pair launch, if it read these lists: tiles 2u and 2u + 1 of a
+    // band, both inside the image
+    const uint64_t tx = ctx->pair_tiles_x;
+    if (ctx->pair_gen == ctx->cand_gen && tx * ctx->pair_bands == ctx->cand_live)
+        for (uint64_t b = 0; b < ctx->pair_bands; ++b)
+            for (uint64_t x = 0; x + 1 < tx; x += 2)
+                out[1] += flags[b * tx + x] & flags[b * tx + x + 1] & rtk::kTileCertain;
     return RT_OK;
 }
 

@@ -56,6 +56,13 @@ struct rt_ctx {
     // rt_set_occlusion_cull: the list build also drops the entries another entry hides from
     // every camera ray of the tile (part of cand_key, with the proofs it needs)
     bool occlusion_cull = true;
+    // rt_set_certain_tiles: where the occlusion rule runs, the list build also flags the
+    // certain tiles for the pair frame loops (part of cand_key)
+    bool certain_tiles = true;
+    // the last tile-pair launch, for rt_certain_tiles_stats: the lists' generation it read,
+    // its tiles per row and its local bands (pair_gen ~0: none yet)
+    uint64_t pair_gen = ~0ull;
+    uint32_t pair_tiles_x = 0, pair_bands = 0;
     // Cost-ordered tiles (TraceParams::tile_order): per-tile durations recorded by the
     // first camera-ray-only launch of a list generation, and the order derived from them.
     uint32_t* tile_cost = nullptr;

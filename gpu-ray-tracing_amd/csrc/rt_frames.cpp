@@ -99,6 +99,12 @@ void note_launch(rt_ctx* ctx, const rtk::TraceParams& p, int kernel, uint32_t fr
     ctx->last.kernel = kernel != rtk::kTraceBounce ? kernel
                        : p.compact == 3u             ? RT_KERNEL_BOUNCE_SPLIT
                                                      : RT_KERNEL_BOUNCE + (int)p.compact;
+    if (kernel == rtk::kTraceListPair2 || kernel == rtk::kTraceListQuad2) {
+        // (rt_certain_tiles_stats: which lists the last tile-pair launch paired, and how)
+        ctx->pair_gen = ctx->cand_gen;
+        ctx->pair_tiles_x = (p.width + 7u) >> 3;
+        ctx->pair_bands = p.local_bands;
+    }
 }
 
 // The context's AQL chain if one-frame updates go through it (rt_set_update_submit AQL, or

@@ -25,6 +25,12 @@ constexpr uint32_t kCandMax = 19;
 constexpr uint32_t kCandRecOff = 1;
 constexpr uint32_t kCandSphOff = 21;
 constexpr uint32_t kCandNone = 0xFFFFFFFFu;
+// Slot 0 beyond the count: .y the entries occlusion removed, .z the tile's flag word — bit 0:
+// the tile is certain (its list is one sphere that every camera ray of the tile certainly
+// hits from outside, front face, near root accepted: rt_occlusion.h), bits 1-2: that
+// sphere's material class as ray_color tests albedo.w (wgsl:272-280).
+constexpr uint32_t kTileCertain = 1u;
+constexpr uint32_t kClassLambertian = 0u, kClassMetal = 1u, kClassDielectric = 2u;
 static_assert(kCandRecOff + ((kCandMax + 3u) & ~3u) <= kCandSphOff, "record chunks fit");
 static_assert(kCandSphOff + 2u * kCandMax <= kCandStride, "sphere records fit");
 // Sample-count hint (see TraceParams::hint_n): per-(frame, bounce) random numbers of the
@@ -241,8 +247,9 @@ hipError_t launch_init(float4* out, uint64_t texels, hipStream_t stream);
 // Builds the per-tile candidate blocks for p's camera/scene/stripes (p.cand_k entries at
 // most per tile).  occlusion: also drop the entries another entry of the tile's list hides
 // from every camera ray of the tile (rt_occlusion.h); the caller has established
-// camera_rays_bounded and the scene bound of TraceParams::roots_fast.
-hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion,
+// camera_rays_bounded and the scene bound of TraceParams::roots_fast.  certain (with
+// occlusion only): also flag the certain tiles (kTileCertain) for the frame loops.
+hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion, bool certain,
                              hipStream_t stream);
 // wg_order for one-frame launches of `pix` tiles per wave: the workgroups by decreasing
 // candidate-list load (per tile 4 + count for a tile with a list, 64 for a tile without

@@ -783,6 +783,108 @@ __device__ __forceinline__ void single_sample(const P& p, const Cam& cam,
     SST_V(5, col[S - 1].x);
 }
 
+// A tile's flag word (kTileCertain and the class, rt_kernels.h) through the constant address
+// space, as load_cnt reads the count beside it.
+__device__ __forceinline__ uint32_t load_flags(const float4* cand, uint32_t tile) {
+    return ((const kconst uint32_t*)cand)[(size_t)tile * (4u * kCandStride) + 2u];
+}
+
+// single_sample<2, true> of a frame loop for a pair of certain tiles (rt_occlusion.h): each
+// tile's list is one sphere that every lane certainly hits from outside, on its front face,
+// with its near root accepted — proven once per camera at list build.  What single_sample
+// decides per lane and frame is therefore known: the walk ends with index 0 and the near
+// root (consider_fast's first quotient, neither test taken), every live lane hits, the normal
+// is the outward one, and the material is the tile's class cls[s], a scalar.  Straight-line:
+// the scan record and the sphere record by scalar loads, no walk, no hit mask, no face test,
+// and the class's scatter alone under a scalar branch.  On every live lane it runs the
+// operations of single_sample and shade_hit on the same operands in the same order: the same
+// bits (lanes outside the image compute values nobody reads, there as here).
+template <typename P>
+__device__ __forceinline__ void certain_sample(const P& p, const Cam& cam,
+                                               const TileCoord (&tc)[2],
+                                               const uint32_t (&hxy)[2],
+                                               const uint32_t (&seed)[2],
+                                               const float4* const (&blk)[2],
+                                               const uint32_t (&cls)[2], const bool (&live)[2],
+                                               const uint64_t (&live_m)[2], v3 (&col)[2]) {
+    constexpr uint32_t S = 2;
+    v3 o[S], d[S];
+    v3 c0 = cam.center;                                           // (as single_sample)
+    asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.z));
+#pragma unroll
+    for (uint32_t s = 0; s < S; ++s)                              // wgsl:311, 305-325
+        get_ray<kSingleDisk>(cam, tc[s].x, tc[s].y, hxy[s], seed[s] * 25u + p.seed_b, o[s],
+                             d[s], &c0);
+    asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c0.z));
+    if (flag_here(p, p.depth) == 0u) {                            // wgsl:264: the sky alone
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s)
+            col[s] = sky_w(mk(1.0f, 1.0f, 1.0f), d[s], dot(d[s], d[s]));
+        return;
+    }
+    const float r_sb = p.rs.x;
+    const v3 ruv = mk(p.rs.y, p.rs.z, p.rs.w);
+#pragma unroll
+    for (uint32_t s = 0; s < S; ++s) {
+        const float a = dot(d[s], d[s]);                          // wgsl:184
+        const float4 g = load_rec<true>(blk[s] + kCandRecOff, 0);
+        const float4 pr = load_rec<true>(blk[s] + kCandSphOff, 0);
+        const float4 mat = load_rec<true>(blk[s] + kCandSphOff, 1);
+        float h;
+        const float disc = discriminant(g, o[s], d[s], a, h);
+        const float q = sqrt_core(disc + 0x1p-126f);              // consider_fast, accepted
+        const float t = div_core(h - q, a, rcp_refined(a));
+        const v3 hp = fmas(t, d[s], o[s]);                        // shade_hit, front face
+        const v3 rel = sub(hp, mk(pr.x, pr.y, pr.z));
+        v3 n;                                                     // wgsl:209
+        if ((__builtin_amdgcn_fcmpf(min_abs3(rel), 0x1p-100f, 4) & live_m[s]) == 0ull) {
+            const float y = rcp_refined(pr.w);
+            n = normal_div(rel, pr.w, y, flag_here(p, p.normal_rn) != 0u);
+        } else {
+            n = divs(rel, pr.w);
+        }
+        const v3 att = mk(mat.x, mat.y, mat.z);
+        if (cls[s] == kClassLambertian) {                         // wgsl:84-93
+            v3 dir = add(n, ruv);
+            float ndd = dot(dir, dir);
+            if ((__builtin_amdgcn_fcmpf(ndd, 0x1.0c6f7ap-20f, 4) & live_m[s]) != 0ull) {
+                asm volatile("");
+                if (ndd < 0x1.0c6f7ap-20f) {                      // wgsl:89-91
+                    dir = n;
+                    ndd = dot(n, n);
+                }
+            }
+            col[s] = sky_w(att, dir, ndd);
+        } else {
+            // (under the live lanes, as shade_hit's per-lane branch runs them: the wave-wide
+            // operand checks of normalize_w see the same lanes)
+            v3 nd = d[s], cf = att;
+            float ndd = a;
+            bool black = false;
+            if (live[s]) {
+                if (cls[s] == kClassMetal) {                      // wgsl:95-100
+                    const v3 refl = fmas(mat.w, ruv, normalize_w<true>(reflect(d[s], n)));
+                    black = !(dot(refl, n) > 0.0f);               // wgsl:277-279
+                    nd = normalize_w<true>(refl);
+                    ndd = dot(nd, nd);
+                } else {                                          // wgsl:102-135, front face
+                    cf = mk(1.0f, 1.0f, 1.0f);
+                    const float ratio = 1.0f / mat.x;
+                    const v3 u = normalize_w<true>(d[s]);
+                    const float cos_t = fminf(dot(neg(u), n), 1.0f);
+                    const float sin_t = sqrtf(fmaf(-cos_t, cos_t, 1.0f));
+                    const bool cannot = ratio * sin_t > 1.0f;
+                    const bool refl = cannot || reflectance(cos_t, ratio) > r_sb;
+                    nd = normalize_w<true>(refl ? reflect(u, n) : refract(u, n, ratio));
+                    ndd = dot(nd, nd);
+                }
+            }
+            const v3 c = sky_w(cf, nd, ndd);
+            col[s] = black ? mk(0.0f, 0.0f, 0.0f) : c;            // wgsl:277-279
+        }
+    }
+}
+
 // kReset: the frame resets the accumulator (camera_has_moved > 0.5, wgsl:345-350) — a
 // separate kernel (rt_single_reset_kernel), so that the steady-state kernel carries no
 // per-pixel selects between the loaded and the zero accumulator, and the reset kernel no
@@ -1106,7 +1208,7 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
     const uint32_t unit = lband * units_x + ux;
     const uint32_t tx0 = ux * S;
     TileCoord tc[S];
-    uint32_t ncand[S], hxy[S], tile[S];
+    uint32_t ncand[S], hxy[S], tile[S], tflags[S];
     const float4* blk[S];
     float4 acc[S];
     uint64_t valid_m[S];
@@ -1118,6 +1220,7 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
         tc[s] = tile_coord(a_width, a_height, band_first, band_step, tx, lband, lane);
         blk[s] = a_cand + (size_t)tile[s] * kCandStride;
         ncand[s] = in ? load_cnt(a_cand, tile[s]) : 0u;
+        tflags[s] = in ? load_flags(a_cand, tile[s]) : 0u;
         acc[s] = a_in[tc[s].valid ? tc[s].idx : 0];               // wgsl:339
         hxy[s] = a_hx[min(tc[s].x, a_width - 1u)] ^                // wgsl:309-310
                  a_hx[hy_offset(a_width) + min(tc[s].y, a_height - 1u)];
@@ -1153,8 +1256,11 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
         // both counts as signed bytes (a count is at most kCandMax, kCandNone is -1) and, from
         // bit 16, tile[1] - tile[0]: 1, or 0 where the partner tile is outside the image
         static_assert(kCandMax < 0x80u && kCandNone == 0xFFFFFFFFu, "a count fits a signed byte");
+        // and, from bits 24 and 27, the tiles' flag words (certain, class: three bits each)
         const uint32_t unit_state =
-            (ncand[0] & 0xFFu) | (ncand[1] & 0xFFu) << 8 | (tile[1] - tile[0]) << 16;
+            (ncand[0] & 0xFFu) | (ncand[1] & 0xFFu) << 8 | (tile[1] - tile[0]) << 16 |
+            (tflags[0] & 7u) << 24 | (tflags[1] & 7u) << 27;
+        constexpr uint32_t kPairCertain = kTileCertain << 24 | kTileCertain << 27;
         for (uint32_t f = 0; f < p.frames; f += Gu) {
             const uint32_t fw = f + w;
             // (single_sample writes every lane's colour; zeros only where nothing is traced)
@@ -1199,12 +1305,18 @@ __global__ __launch_bounds__(64 * G, RT_TPAIR_MIN_WAVES) void rt_tpair_kernel(
                     asm volatile("" : "+s"(t0), "+s"(st));
 #pragma unroll
                     for (uint32_t s = 0; s < S; ++s) {
-                        const uint32_t t = t0 + (s ? st >> 16 : 0u);
+                        const uint32_t t = t0 + (s ? (st >> 16) & 1u : 0u);
                         blkf[s] = a_cand + (size_t)t * kCandStride;
                         ncf[s] = (uint32_t)((int32_t)(st << (24u - 8u * s)) >> 24);
                     }
-                    single_sample<S, true>(v, cam, tc, hxy, seed, blkf, ncf, live, valid_m, bv,
-                                           nullptr, col);
+                    if ((st & kPairCertain) == kPairCertain) {
+                        // both tiles certain: the straight-line sample (certain_sample)
+                        const uint32_t cls[S] = {(st >> 25) & 3u, (st >> 28) & 3u};
+                        certain_sample(v, cam, tc, hxy, seed, blkf, cls, live, valid_m, col);
+                    } else {
+                        single_sample<S, true>(v, cam, tc, hxy, seed, blkf, ncf, live, valid_m,
+                                               bv, nullptr, col);
+                    }
                 }
             }
             // two LDS slots alternating by group (one barrier per group, as trace_pair): wave w
@@ -2019,6 +2131,9 @@ __global__ __launch_bounds__(256) void rt_wg_cost_kernel(const float4* __restric
 // exceeds it), closes the gaps in place (index order kept, each entry's sphere record beside
 // its scan record as before) and leaves the number dropped in the count word's .y (u32 bits;
 // rt_occlusion_cull_stats).  A tile without a list, or whose cone is degenerate, is left alone.
+// occl bit 1 (rt_set_certain_tiles, with bit 0 only): a tile whose list is then one entry that
+// every ray certainly hits on its front face is flagged certain, with the entry's material
+// class, in the count word's .z (rt_occlusion.h certainly_front; rt_certain_tiles_stats).
 #ifndef RT_CAND_BX
 #define RT_CAND_BX 8
 #endif
@@ -2111,17 +2226,22 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
     }
     if (!mine) return;
     uint32_t removed = 0;
-    if (occl && ok && n <= K && n >= 2u) {
+    // certain tiles: whether the one entry left certainly shows every ray its front face — the
+    // occluder's, from the bounds the cull computes anyway
+    bool front_one = false;
+    if ((occl & 1u) && ok && n <= K && n >= 2u) {
         const Lens lens = bundle_lens(p, k);
         // the occluder: the smallest upper bound among the entries every ray certainly hits
         float t_occ = __builtin_inff();
         uint32_t j_occ = kCandNone;
         for (uint32_t j = 0; j < n; ++j) {
-            const OccBounds b = occ_bounds(k, lens, s_own[j][lane]);
+            const float4 gj = s_own[j][lane];
+            const OccBounds b = occ_bounds(k, lens, gj);
             s_lo[j][lane] = b.lo;
             if (b.covers && b.hi < t_occ) {
                 t_occ = b.hi;
                 j_occ = j;
+                front_one = certainly_front(b, gj);
             }
         }
         if (j_occ != kCandNone) {
@@ -2136,15 +2256,29 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
                 ++m;
             }
             removed = n - m;
-            n = m;
+            n = m;   // (the occluder is never dropped: a list of one is the occluder)
         }
+    } else if (occl == 3u && ok && n == 1u && n <= K) {
+        // a list of one from the start: nothing to cull, its bounds for the flag alone
+        const float4 g = s_own[0][lane];
+        front_one = certainly_front(occ_bounds(k, bundle_lens(p, k), g), g);
+    }
+    // a certain tile (rt_occlusion.h): one entry left, every ray certainly hits it from
+    // outside on its front face with the near root accepted; a negative radius flips the
+    // normal (wgsl:209 divides by it), so such a tile stays general
+    uint32_t flags = 0;
+    if ((occl & 2u) && ok && n <= K && n == 1u && front_one) {
+        const float radius = sph[0].w, matw = sph[1].w;
+        if (radius > 0.0f && __builtin_isfinite(radius))
+            flags = kTileCertain | material_class(matw) << 1;
     }
     const uint32_t c = ok && n <= K ? n : kCandNone;
     // zero the chunk padding after the last record
     if (c != kCandNone)
         for (uint32_t q = n; q < ((n + 3u) & ~3u); ++q)
             rec[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    own[0] = make_float4(__uint_as_float(c), __uint_as_float(removed), 0.0f, 0.0f);
+    own[0] = make_float4(__uint_as_float(c), __uint_as_float(removed), __uint_as_float(flags),
+                         0.0f);
 }
 
 __global__ __launch_bounds__(256) void rt_init_kernel(float4* __restrict__ out, uint64_t n) {
@@ -2577,14 +2711,14 @@ hipError_t launch_trace(const TraceParams& p, int kernel, hipStream_t stream) {
     return launch_trace_as<kTraceExhaustive>(p, 0, stream);
 }
 
-hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion,
+hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion, bool certain,
                              hipStream_t stream) {
     const uint32_t tiles_x = (p.width + 7u) >> 3;
     const dim3 grid((tiles_x + kCandBX - 1u) / kCandBX,
                     (p.local_bands + kCandBY - 1u) / kCandBY);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_candidates_kernel, grid, dim3(64), 0, stream, p, cand,
-                       occlusion ? 1u : 0u);
+                       occlusion ? (certain ? 3u : 1u) : 0u);
     return hipGetLastError();
 }
 

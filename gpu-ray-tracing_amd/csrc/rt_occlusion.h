@@ -33,6 +33,25 @@
 // the true q = sqrt(R^2 - dl^2) is known to be at least q, and by at most sqrt(E') anywhere;
 // h, the subtraction, a and the division add less than 9 eps (s + R).  occ_bounds() takes
 // E = 2e-6 (s^2 + R^2) >= 2 E' and 1e-6 (s + R) > 16 eps (s + R).
+//
+// Certain tiles (certainly_front below).  A tile whose culled list is one entry S
+// with (a), of positive finite radius, needs no hit test in the frame loop: every lane's walk
+// ends with index 0 and S's near root.  The frame loop's straight-line sample also skips the
+// face test (wgsl:210-216), so the list build proves its outcome too: the computed
+// dot(d, outward) is negative in every lane.  With u = d / |d| the true value is -|d| q / R,
+// q = sqrt(R^2 - dl^2) the half chord, at least q_lo = sqrt(R^2 - dl_hi^2) (q_lo^2 > E by
+// `inside`).  The computed value, scaled by R / |d|, differs from -q by at most
+//   D   the computed root's error as a distance, along u itself: at most `err` above;
+//   2^-24 (l1(C) + 3 (R + D))   the fma of hp = o + root d, a single rounding per component of a
+//       value within R + D of C (the camera and the centre may lie far from the origin: this
+//       term scales with the coordinates, not with s);
+//   2^-24 sqrt(3) (R + D)   the subtraction rel = hp - C;
+//   2^-24 2 R   the division by R (correctly rounded by either form, normal_div or IEEE);
+//   2^-24 4 R   the dot product's three roundings, each of a partial sum of at most |d| 1.01;
+// together less than err + 1e-6 (l1(C) + R).  certainly_front() asks for twice that under
+// 0.9 q_lo (q2's own f32 error is at most 2 eps R^2 < 0.06 E, and the hardware square root's
+// an ulp).  Nothing here can underflow: |d|^2 >= 2^-11 (camera_rays_bounded) and q / R >
+// sqrt(2e-6), so the sum's leading term is far above the normal range's floor.
 #pragma once
 
 #include "rt_trace_device.h"
@@ -66,15 +85,18 @@ __device__ __forceinline__ Lens bundle_lens(const TraceParams& p, const Cone& k)
 //   lo  <= the computed near root of any ray that the entry could win with (-inf: unknown)
 //   hi  >= the computed near root of every ray, valid when `covers`
 //   covers: (a) above holds for this entry
+//   q2, err: R^2 - dl_hi^2 and the root's error bound, for certainly_front (valid when `covers`)
 struct OccBounds {
     float lo, hi;
     bool covers;
+    float q2, err;
 };
 __device__ __forceinline__ OccBounds occ_bounds(const Cone& k, const Lens& b, float4 g) {
     OccBounds r;
     r.lo = -__builtin_inff();
     r.hi = __builtin_inff();
     r.covers = false;
+    r.q2 = r.err = 0.0f;
     const v3 C = mk(g.x, g.y, g.z);
     const float R2 = g.w, R = __builtin_amdgcn_sqrtf(g.w);        // |radius|
     // the ray lines, from the apex (the cross product: no cancellation in p)
@@ -115,8 +137,24 @@ __device__ __forceinline__ OccBounds occ_bounds(const Cone& k, const Lens& b, fl
         r.hi = fminf(num / den, tangent) * 1.0001f + err;
         // the near root (distance / |d|, |d| <= d_max) certainly exceeds 0.001
         r.covers = s_lo - R - err > 1.1e-3f * k.d_max && __builtin_isfinite(r.hi);
+        r.q2 = q2;
+        r.err = err;
     }
     return r;
+}
+
+// The computed dot(d, outward) of an entry with `covers` is negative in every lane (the
+// header's argument).  g: the entry's scan record, b: its bounds.
+__device__ __forceinline__ bool certainly_front(const OccBounds& b, float4 g) {
+    const float R = __builtin_amdgcn_sqrtf(g.w);
+    return b.covers && 0.9f * __builtin_amdgcn_sqrtf(b.q2) >
+                           2.0f * (b.err + 1e-6f * (l1(mk(g.x, g.y, g.z)) + R));
+}
+
+// The material class of a tile's flag word (rt_kernels.h), as ray_color tests albedo.w
+// (wgsl:272-280; a NaN is a dielectric there)
+__device__ __forceinline__ uint32_t material_class(float w) {
+    return w < -1.0f ? kClassLambertian : w <= 1.0f ? kClassMetal : kClassDielectric;
 }
 
 }  // namespace rtk

@@ -159,6 +159,12 @@ _SIGS_OCCLUSION = {
     "rt_occlusion_cull_stats": (ctypes.c_int, [P, P]),
 }
 
+# include/rt_certain_tiles.h
+_SIGS_CERTAIN = {
+    "rt_set_certain_tiles": (ctypes.c_int, [P, ctypes.c_int]),
+    "rt_certain_tiles_stats": (ctypes.c_int, [P, P]),
+}
+
 # include/rt_selftest_roots.h
 _SIGS_SELFTEST_ROOTS = {
     "rt_selftest_roots": (ctypes.c_int, [P, ctypes.c_uint64, P]),
@@ -409,7 +415,7 @@ def lib() -> ctypes.CDLL:
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
                                   **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION,
-                                  **_SIGS_MATTE, **_SIGS_QUERY}.items():
+                                  **_SIGS_MATTE, **_SIGS_QUERY, **_SIGS_CERTAIN}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -456,6 +462,10 @@ def chain_parts_symbols() -> list[str]:
 
 def occlusion_symbols() -> list[str]:
     return list(_SIGS_OCCLUSION)
+
+
+def certain_symbols() -> list[str]:
+    return list(_SIGS_CERTAIN)
 
 
 def selftest_roots_symbols() -> list[str]:

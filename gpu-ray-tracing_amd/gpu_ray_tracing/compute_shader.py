@@ -245,6 +245,21 @@ class ComputeShaderPipeline:
         entry hides from every camera ray of the tile (default on); identical pixels."""
         _lib.call("rt_set_occlusion_cull", self._ctx, 1 if on else 0)
 
+    def set_certain_tiles(self, on: bool) -> None:
+        """rt_set_certain_tiles: whether the list build marks the tiles one sphere certainly
+        covers and the pair frame loops trace them straight-line (default on); identical
+        pixels."""
+        if hasattr(_lib.lib(), "rt_set_certain_tiles"):       # (absent from older builds)
+            _lib.call("rt_set_certain_tiles", self._ctx, 1 if on else 0)
+
+    def certain_tiles_stats(self) -> dict:
+        """rt_certain_tiles_stats: certain tiles of the lists built last, and pairs of two
+        certain tiles in the last tile-pair launch."""
+        out = (ctypes.c_uint64 * 2)()
+        if hasattr(_lib.lib(), "rt_certain_tiles_stats"):     # (absent from older builds)
+            _lib.call("rt_certain_tiles_stats", self._ctx, out)
+        return {"certain_tiles": int(out[0]), "certain_pairs": int(out[1])}
+
     def set_update_submit(self, mode: str) -> None:
         """rt_set_update_submit: how update_frames submits one-frame updates — "auto" (HIP
         launches; AQL is opt-in), "hip" or "aql" (AQL packets on the context's own HSA
