@@ -24,6 +24,7 @@
 #include "rt_certain_tiles.h"
 #include "rt_occlusion_cull.h"
 #include "rt_selftest_roots.h"
+#include "rt_tile_lists.h"
 
 namespace {
 thread_local std::string g_last_error = "";
@@ -230,6 +231,46 @@ rt_status rt_certain_tiles_stats(rt_ctx* ctx, uint64_t out[2]) {
         for (uint64_t b = 0; b < ctx->pair_bands; ++b)
             for (uint64_t x = 0; x + 1 < tx; x += 2)
                 out[1] += flags[b * tx + x] & flags[b * tx + x + 1] & rtk::kTileCertain;
+    return RT_OK;
+}
+
+rt_status rt_set_tight_bundle(rt_ctx* ctx, int on) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (on != 0 && on != 1) return fail(RT_ERR_INVALID_ARGUMENT, "on must be 0 or 1");
+    ctx->tight_bundle = on != 0;     // (part of the lists' key: the next trace call rebuilds them)
+    return RT_OK;
+}
+
+// an rt_tile_list is the head of a tile's candidate block: the count word's float4, then the
+// scan records
+static_assert(RT_TILE_LIST_MAX == rtk::kCandMax && rtk::kCandRecOff == 1u &&
+                  sizeof(rt_tile_list) == (1u + rtk::kCandMax) * sizeof(float4) &&
+                  RT_TILE_LIST_NONE == rtk::kCandNone && RT_TILE_CERTAIN == rtk::kTileCertain,
+              "rt_tile_list mirrors the candidate block");
+
+rt_status rt_tile_lists(rt_ctx* ctx, rt_tile_list* out, uint64_t capacity, uint64_t* tiles) {
+    if (!ctx) return fail(RT_ERR_INVALID_CONTEXT, "ctx is NULL");
+    if (!tiles) return fail(RT_ERR_INVALID_ARGUMENT, "tiles is NULL");
+    *tiles = 0;
+    // (RT_SCAN_EXHAUSTIVE reads no lists: whatever an earlier build left is not in use)
+    if (!ctx->cand || ctx->cand_live == 0 || ctx->scan_mode != RT_SCAN_CULLED) return RT_OK;
+    *tiles = ctx->cand_live;
+    const uint64_t n = std::min<uint64_t>(ctx->cand_live, capacity);
+    if (!out || n == 0) return RT_OK;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(RT_ERR_INVALID_DEVICE, "hipSetDevice failed");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy2D(out, sizeof(rt_tile_list), ctx->cand, rtk::kCandStride * sizeof(float4),
+                        sizeof(rt_tile_list), n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy2D(tile lists)");
+    for (uint64_t t = 0; t < n; ++t) {
+        rt_tile_list& l = out[t];
+        l.reserved = 0;
+        const uint32_t kept = l.count == RT_TILE_LIST_NONE ? 0u : std::min(l.count, RT_TILE_LIST_MAX);
+        if (kept < RT_TILE_LIST_MAX)
+            std::memset(l.records[kept], 0, (RT_TILE_LIST_MAX - kept) * sizeof(l.records[0]));
+    }
     return RT_OK;
 }
 

@@ -59,6 +59,9 @@ struct rt_ctx {
     // rt_set_certain_tiles: where the occlusion rule runs, the list build also flags the
     // certain tiles for the pair frame loops (part of cand_key)
     bool certain_tiles = true;
+    // rt_set_tight_bundle: the lists are built against the two-slope beam of a tile's camera
+    // rays, else against the single cone (part of cand_key)
+    bool tight_bundle = true;
     // the last tile-pair launch, for rt_certain_tiles_stats: the lists' generation it read,
     // its tiles per row and its local bands (pair_gen ~0: none yet)
     uint64_t pair_gen = ~0ull;

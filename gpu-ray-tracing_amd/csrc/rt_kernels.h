@@ -248,9 +248,10 @@ hipError_t launch_init(float4* out, uint64_t texels, hipStream_t stream);
 // most per tile).  occlusion: also drop the entries another entry of the tile's list hides
 // from every camera ray of the tile (rt_occlusion.h); the caller has established
 // camera_rays_bounded and the scene bound of TraceParams::roots_fast.  certain (with
-// occlusion only): also flag the certain tiles (kTileCertain) for the frame loops.
+// occlusion only): also flag the certain tiles (kTileCertain) for the frame loops.  tight: the
+// tiles' bundles are the two-slope beam (rt_trace_device.h footprint_beam), else the single cone.
 hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion, bool certain,
-                             hipStream_t stream);
+                             bool tight, hipStream_t stream);
 // wg_order for one-frame launches of `pix` tiles per wave: the workgroups by decreasing
 // candidate-list load (per tile 4 + count for a tile with a list, 64 for a tile without
 // one), sorted by launch_tile_order's buckets;

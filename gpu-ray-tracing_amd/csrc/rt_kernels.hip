@@ -2111,7 +2111,7 @@ __global__ __launch_bounds__(256) void rt_wg_cost_kernel(const float4* __restric
     cost[u] = sum;
 }
 
-// List the spheres the camera rays of each tile can hit (see footprint_cone).
+// List the spheres the camera rays of each tile can hit (see footprint_beam).
 // One wave per block of 8 x 8 tiles (8 columns of tiles x 8 local bands), one lane per
 // tile.  The wave first tests the spheres, 64 at a time, against the cone of the whole
 // block's footprint and stages the survivors (scan + sphere records, index order) in LDS,
@@ -2134,6 +2134,8 @@ __global__ __launch_bounds__(256) void rt_wg_cost_kernel(const float4* __restric
 // occl bit 1 (rt_set_certain_tiles, with bit 0 only): a tile whose list is then one entry that
 // every ray certainly hits on its front face is flagged certain, with the entry's material
 // class, in the count word's .z (rt_occlusion.h certainly_front; rt_certain_tiles_stats).
+// occl bit 2 (rt_set_tight_bundle off): the block's and the tiles' bundles are the single cone
+// with the wider lens radius instead of the two-slope beam (footprint_beam's `parent`).
 #ifndef RT_CAND_BX
 #define RT_CAND_BX 8
 #endif
@@ -2166,15 +2168,16 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
     const auto row0 = [&](uint32_t lb) {
         return (float)((p.band_first + lb * p.band_step) * RT_STRIPE_ROWS);
     };
-    Cone kb;
-    const bool in_blk = footprint_cone(p, (float)(tx0 * 8u), (float)(tx1 * 8u), row0(lb0),
-                                    row0(lb1 - 1u) + 8.0f, kb);
+    const bool parent = (occl & 4u) != 0u;
+    Beam kb;
+    const bool in_blk = footprint_beam(p, (float)(tx0 * 8u), (float)(tx1 * 8u), row0(lb0),
+                                    row0(lb1 - 1u) + 8.0f, parent, kb);
     // this lane's tile and its cone
     const uint32_t tx = tx0 + lane % kCandBX, lb = lb0 + lane / kCandBX;
     const bool mine = tx < tx1 && lb < lb1;
-    Cone k;
-    const bool ok = mine && footprint_cone(p, (float)(tx * 8u), (float)(tx * 8u + 8u), row0(lb),
-                                           row0(lb) + 8.0f, k);
+    Beam k;
+    const bool ok = mine && footprint_beam(p, (float)(tx * 8u), (float)(tx * 8u + 8u), row0(lb),
+                                           row0(lb) + 8.0f, parent, k);
     const uint32_t tile = lb * tiles_x + tx;
     const uint32_t K = min(p.cand_k, kCandMax);
     float4* const own = cand + (size_t)tile * kCandStride;
@@ -2193,7 +2196,7 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
 #pragma unroll
         for (uint32_t b = 0; b < kCandGroup; ++b) {             // block-cone survivors
             const uint32_t i = gbase + b * 64u + lane;
-            const bool keep = i < count && (!in_blk || !cone_misses(kb, gv[b]));
+            const bool keep = i < count && (!in_blk || !beam_misses(kb, gv[b]));
             const unsigned long long mask = rt_ballot(keep);
             if (keep) {
                 const uint32_t pos = m + __builtin_amdgcn_mbcnt_hi(
@@ -2212,7 +2215,7 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
         __syncthreads();
         for (uint32_t j = 0; j < m; ++j) {                      // this lane's tile test
             const float4 gj = s_rec[j];
-            if (ok && !cone_misses(k, gj)) {
+            if (ok && !beam_misses(k, gj)) {
                 if (n < K) {
                     rec[n] = gj;
                     s_own[n][lane] = gj;
@@ -2230,7 +2233,7 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
     // occluder's, from the bounds the cull computes anyway
     bool front_one = false;
     if ((occl & 1u) && ok && n <= K && n >= 2u) {
-        const Lens lens = bundle_lens(p, k);
+        const Lens lens = bundle_lens(p, k, parent);
         // the occluder: the smallest upper bound among the entries every ray certainly hits
         float t_occ = __builtin_inff();
         uint32_t j_occ = kCandNone;
@@ -2258,10 +2261,10 @@ __global__ __launch_bounds__(64) void rt_candidates_kernel(const TraceParams p,
             removed = n - m;
             n = m;   // (the occluder is never dropped: a list of one is the occluder)
         }
-    } else if (occl == 3u && ok && n == 1u && n <= K) {
+    } else if ((occl & 3u) == 3u && ok && n == 1u && n <= K) {
         // a list of one from the start: nothing to cull, its bounds for the flag alone
         const float4 g = s_own[0][lane];
-        front_one = certainly_front(occ_bounds(k, bundle_lens(p, k), g), g);
+        front_one = certainly_front(occ_bounds(k, bundle_lens(p, k, parent), g), g);
     }
     // a certain tile (rt_occlusion.h): one entry left, every ray certainly hits it from
     // outside on its front face with the near root accepted; a negative radius flips the
@@ -2712,13 +2715,13 @@ hipError_t launch_trace(const TraceParams& p, int kernel, hipStream_t stream) {
 }
 
 hipError_t launch_candidates(const TraceParams& p, float4* cand, bool occlusion, bool certain,
-                             hipStream_t stream) {
+                             bool tight, hipStream_t stream) {
     const uint32_t tiles_x = (p.width + 7u) >> 3;
     const dim3 grid((tiles_x + kCandBX - 1u) / kCandBX,
                     (p.local_bands + kCandBY - 1u) / kCandBY);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_candidates_kernel, grid, dim3(64), 0, stream, p, cand,
-                       occlusion ? (certain ? 3u : 1u) : 0u);
+                       (occlusion ? (certain ? 3u : 1u) : 0u) | (tight ? 0u : 4u));
     return hipGetLastError();
 }
 

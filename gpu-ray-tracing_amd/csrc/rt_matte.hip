@@ -13,10 +13,11 @@ namespace {
 
 constexpr uint32_t kMiss = 0xFFFFFFFFu;          // RT_AOV_MISS
 
-// footprint_cone (rt_trace_device.h) for a parameter block other than TraceParams: the cone of
-// every camera ray through the focus-plane rectangle of pixel columns [x0, x1) and rows [y0, y1),
-// whatever the jitter, the lens point and the frame seed.  The construction and its margins are
-// footprint_cone's, restated here so that the shared header stays as it is.
+// The single cone of footprint_beam (rt_trace_device.h, its `parent` form) for a parameter block
+// other than TraceParams: the cone of every camera ray through the focus-plane rectangle of pixel
+// columns [x0, x1) and rows [y0, y1), whatever the jitter, the lens point and the frame seed.  The
+// construction and its margins are that form's, restated here so that the shared header stays as
+// it is.
 template <typename P>
 __device__ __forceinline__ bool footprint_cone_of(const P& p, float x0, float x1, float y0,
                                                   float y1, Cone& k) {

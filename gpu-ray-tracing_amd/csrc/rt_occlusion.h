@@ -3,7 +3,7 @@
 // render kernels' unit only and used by the list build alone: the per-frame kernels read
 // shorter lists and are not otherwise touched.
 //
-// cone_misses() asks whether a camera ray of the tile could touch a sphere; it never asks
+// beam_misses() asks whether a camera ray of the tile could touch a sphere; it never asks
 // whether the sphere could be the first hit.  An entry O of a tile's list is dropped when
 // another entry S of the same list provably wins against it in every lane and frame:
 //   (a) every ray of the tile's bundle hits S with a discriminant that is certainly positive
@@ -15,17 +15,24 @@
 // replaces it (root_S < root_O = tmax); after S, O fails `tmax <= root` (tmax <= root_S).
 // The separation is strict, so the first-index tie rule never decides between them.
 //
-// The bundle of a tile (footprint_cone): every ray line passes within r_o of the apex (the
-// footprint centre on the focus plane) with a unit direction within theta of the axis, and
-// every origin lies within rl of the camera centre.  For a sphere (C, R), a ray with origin o
-// and unit direction u: s = |C - o|, dl = the distance of C from the ray's line.  A ray that
-// heads towards C from outside hits at distance near(s, dl) = sqrt(s^2 - dl^2) - sqrt(R^2 -
-// dl^2), increasing in s and in dl (R < s), and evaluated as (s - R)(s + R) / (sqrt(s^2 - dl^2)
+// The bundle of a tile (footprint_beam, rt_trace_device.h): every ray's line lies in the union
+// of the balls of radius rho(t) about the axis point at t from the apex (the footprint centre on
+// the focus plane; rho: the two-slope beam, or with rt_set_tight_bundle off the single cone),
+// every direction lies within theta of the axis (sin theta = the beam's far slope), and every
+// origin lies within rl of the camera centre (bundle_lens: the lens radius of lens_radius(),
+// widened as footprint_beam widens its own).  For a sphere (C, R), a ray with origin o and unit
+// direction u: s = |C - o|, dl = the distance of C from the ray's line.  A ray that heads
+// towards C from outside hits at distance near(s, dl) = sqrt(s^2 - dl^2) - sqrt(R^2 - dl^2),
+// increasing in s and in dl (R < s), and evaluated as (s - R)(s + R) / (sqrt(s^2 - dl^2)
 // + sqrt(R^2 - dl^2)) without cancellation (the ground: s - R = 2 of 1000).  Over the bundle
-// s lies in [D - rl, D + rl] (D = |C - centre|) and dl in [p cos - |t| sin - r_o,
-// p + |t| sin + r_o] (t, p: C along and across the axis from the apex — cone_misses' lower
-// bound and its mirror image), so near() at the lower corner bounds O's near hit from below
-// and near() at the upper corner bounds S's from above (never above the tangent length).
+// s lies in [D - rl, D + rl] (D = |C - centre|).  dl lies in [p cos - rho(t), p + rho(t)]
+// (t, p: C along and across the axis from the apex): the lower end is beam_misses' bound; the
+// upper end holds because the line's point with the axis parameter of t lies within rho(t) of
+// the axis point at t, which lies p from C, and dl is at most the distance to any point of the
+// line.  So near() at the lower corner bounds O's near hit from below and near() at the upper
+// corner bounds S's from above (never above the tangent length).  `ahead`: with tc, pc the
+// centre along and across the axis from the camera centre, (C - o).u >= tc cos - pc sin - rl
+// for every direction within theta of the axis and every origin within rl of the centre.
 //
 // f32 error of the computed root, as a distance (root |d|; both roots of a lane share d and
 // the computed a, so comparing distances compares roots): the discriminant's error is
@@ -63,20 +70,16 @@ __device__ __forceinline__ v3 cross3(v3 a, v3 b) {
 }
 __device__ __forceinline__ float l1(v3 v) { return fabsf(v.x) + fabsf(v.y) + fabsf(v.z); }
 
-// What the occlusion rule needs beyond the tile's Cone: the camera centre and the radius of
-// the lens disk about it, widened exactly as footprint_cone widens its own.
+// What the occlusion rule needs beyond the tile's Beam: the camera centre and the radius of
+// the lens disk about it, widened exactly as footprint_beam widens its own.
 struct Lens {
     v3 ctr;
     float rl;
 };
-__device__ __forceinline__ Lens bundle_lens(const TraceParams& p, const Cone& k) {
+__device__ __forceinline__ Lens bundle_lens(const TraceParams& p, const Beam& k, bool parent) {
     Lens b;
     b.ctr = mk(p.center[0], p.center[1], p.center[2]);
-    float rl = 0.0f;
-    if (p.defocus_angle > 0.0f) {
-        const v3 du = mk(p.ddu[0], p.ddu[1], p.ddu[2]), dv = mk(p.ddv[0], p.ddv[1], p.ddv[2]);
-        rl = __builtin_amdgcn_sqrtf(dot(du, du) + dot(dv, dv));
-    }
+    const float rl = lens_radius(p, parent);
     b.rl = rl * 1.001f + 1e-5f * (l1(k.apex) + l1(b.ctr));
     return b;
 }
@@ -91,7 +94,7 @@ struct OccBounds {
     bool covers;
     float q2, err;
 };
-__device__ __forceinline__ OccBounds occ_bounds(const Cone& k, const Lens& b, float4 g) {
+__device__ __forceinline__ OccBounds occ_bounds(const Beam& k, const Lens& b, float4 g) {
     OccBounds r;
     r.lo = -__builtin_inff();
     r.hi = __builtin_inff();
@@ -101,10 +104,11 @@ __device__ __forceinline__ OccBounds occ_bounds(const Cone& k, const Lens& b, fl
     const float R2 = g.w, R = __builtin_amdgcn_sqrtf(g.w);        // |radius|
     // the ray lines, from the apex (the cross product: no cancellation in p)
     const v3 v = sub(C, k.apex);
-    const float at = fabsf(dot(v, k.axis)), p = len3(cross3(v, k.axis));
+    const float t = dot(v, k.axis), at = fabsf(t), p = len3(cross3(v, k.axis));
+    const float spread = beam_spread(k, t);   // rho(t) - r_o, the beam at the centre's position
     const float sl = 1e-5f * (at + p + k.r_o) + 1e-6f * (l1(C) + l1(k.apex));
-    const float dl_hi = p + at * k.sin_t + k.r_o + sl;
-    const float dl_lo = fmaf(p, k.cos_t, -at * k.sin_t) - k.r_o - sl;
+    const float dl_hi = p + spread + k.r_o + sl;
+    const float dl_lo = fmaf(p, k.cos_t, -spread) - k.r_o - sl;
     // the origins, from the camera centre
     const v3 w = sub(C, b.ctr);
     const float D = len3(w), tc = dot(w, k.axis), pc = len3(cross3(w, k.axis));

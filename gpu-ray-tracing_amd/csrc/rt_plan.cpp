@@ -97,7 +97,7 @@ void free_candidates(rt_ctx* ctx) {
 static rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t stream) {
     struct Key {
         float center[3], vul[3], pdu[3], pdv[3], ddu[3], ddv[3], defocus;
-        uint32_t w, h, first, step, bands, occlusion, certain;
+        uint32_t w, h, first, step, bands, occlusion, certain, tight;
         uint64_t scene;
     } key;
     std::memset(&key, 0, sizeof(key));
@@ -122,6 +122,7 @@ static rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t
     // (certain tiles are a by-product of the occlusion rule's bounds: flagged only where it runs)
     const bool certain = occlusion && ctx->certain_tiles;
     key.certain = certain ? 1u : 0u;
+    key.tight = ctx->tight_bundle ? 1u : 0u;
     const unsigned char* kb = reinterpret_cast<const unsigned char*>(&key);
     const uint64_t tiles = launch_tiles(p.width, p.local_bands);
     p.cand_k = rtk::kCandMax;
@@ -140,7 +141,8 @@ static rt_status ensure_candidates(rt_ctx* ctx, rtk::TraceParams& p, hipStream_t
             }
             ctx->cand_tiles = tiles;
         }
-        hipError_t e = rtk::launch_candidates(p, ctx->cand, occlusion, certain, stream);
+        hipError_t e = rtk::launch_candidates(p, ctx->cand, occlusion, certain,
+                                              ctx->tight_bundle, stream);
         if (e != hipSuccess) return hip_fail(e, "rt_candidates_kernel launch");
         ctx->cand_key.assign(kb, kb + sizeof(key));
         ctx->cand_gen++;

@@ -715,19 +715,77 @@ __device__ __forceinline__ Hit scan_culled(const GridP& gp, const float4* __rest
 //
 // Every camera ray of a tile passes through the tile's footprint on the focus plane
 // (pc = vul + pdu*sx + pdv*sy with sx in [x0, x0+8], sy in [y0, y0+8] for any jitter, since
-// rounding is monotonic) and through the lens disk (|o - center| <= |(px,py)| *
-// sqrt(|ddu|^2 + |ddv|^2)), whatever the frame seed.  That gives a cone valid for ALL
-// frames of a camera: apex = footprint centre Pc, r_O = footprint radius, axis =
-// Pc - center, sin(theta) <= (r_O + r_lens) / (|Pc - center| - r_O - r_lens).  Spheres
-// that cone_misses() rejects can never be hit by a camera ray of the tile; the others are
-// listed (records + indices, in index order) once per camera/scene by
+// rounding is monotonic): q with |q - Pc| <= r_q, Pc the footprint's centre, and starts on the
+// lens disk: o = center + ux ddu + uy ddv with |o - center| <= r_l, whatever the frame seed.
+//
+// The lens radius.  |ux ddu + uy ddv| <= sigma |(ux, uy)|, sigma the largest singular value of
+// the 3 x 2 matrix [ddu ddv]: the square root of the largest eigenvalue of its Gram matrix
+// [[a c] [c b]] (a = |ddu|^2, b = |ddv|^2, c = ddu.ddv), (a + b) / 2 + sqrt(((a - b) / 2)^2 +
+// c^2).  For orthogonal vectors of one length that is the length itself, where sqrt(a + b),
+// the bound used before, is sqrt(2) of it.  disk_unit's computed (ux, uy) has a length within
+// a few ulp of 1 and the f32 evaluation of the eigenvalue errs by a few ulp of a + b <= twice
+// the eigenvalue: lens_radius() returns 1.0001 sigma, and the callers widen it further.
+//
+// The beam.  The ray's line is x(l) = (1 - l) o + l q over all real l, and the point of the
+// axis line with the same parameter is a(l) = (1 - l) center + l Pc, so
+//     |x(l) - a(l)| <= |1 - l| r_l + |l| r_q  =: rho.
+// Nothing else is used: neither that the lens and the focus plane are parallel nor that ddu
+// and ddv lie in a plane across the axis.  With L = |Pc - center| and t = (l - 1) L, the
+// position of a(l) along the axis from Pc (positive beyond the focus plane), rho is the
+// largest of three straight lines in t:
+//     far    r_q + t (r_l + r_q) / L      (|1 - l| = l - 1, |l| = l:  beyond the focus plane)
+//     near   r_q - t (r_l - r_q) / L      (1 - l, l:   between the lens and the focus plane)
+//     back  -r_q - t (r_l + r_q) / L      (1 - l, -l:  behind the lens)
+// (the fourth combination is the negative of `near` and never the largest of a set whose
+// maximum is >= 0).  So every ray lies in the union over t of the balls of radius rho(t) about
+// the axis point at t.  For a sphere centre C at t along and p across the axis, a line
+// c + s t' of that set with |s| <= sin(theta) and any axis position t' = t - u:
+//     sqrt(p^2 + u^2) - (c + s t') >= p cos + |u| sin - c - s t + s u >= p cos - (c + s t),
+// by Cauchy-Schwarz and |s u| <= |u| sin.  Hence every ray line stays at least
+//     p cos(theta) - rho(t)
+// from C, theta the angle of the steepest line: sin(theta) = (r_l + r_q) / L.  The single
+// cone used before (kept as `parent`, and the one rt_matte.hip restates) is the far line's
+// slope on both sides of Pc with L - r_l - r_q for L; between the lens and the focus plane
+// the beam in truth narrows or widens by (r_l - r_q) / L only, and there the largest spheres
+// on screen lie.  The same sin(theta) bounds the angle between any ray's direction q - o and
+// the axis (|q - o - (Pc - center)| <= r_l + r_q against |Pc - center| = L).
+//
+// f32: r_q and r_l are widened by 0.1 % and by 1e-5 of the coordinates' magnitudes (the
+// evaluation of pc and of o = pc - d + d), the slopes by 1 % upwards — the near slope, when
+// negative, towards zero — and cos(theta) by 0.1 % downwards; the beam is built only where
+// L > 4 (r_q + r_l) and everything is finite, else the tile gets no list.
+//
+// Spheres that beam_misses() rejects can never be hit by a camera ray of the tile; the others
+// are listed (records + indices, in index order) once per camera/scene by
 // rt_candidates_kernel, and each frame's camera rays test only that list.
 __device__ __forceinline__ float len3(v3 v) { return __builtin_amdgcn_sqrtf(dot(v, v)); }
 
-// The cone of the camera rays through the focus-plane rectangle of pixel columns [x0, x1)
-// and rows [y0, y1) (one tile: 8 x 8).
-__device__ __forceinline__ bool footprint_cone(const TraceParams& p, float x0, float x1,
-                                               float y0, float y1, Cone& k) {
+// The radius of the lens disk about the camera centre (0 without a lens), not yet widened for
+// the f32 evaluation of the origins.  parent: the bound used before the beam.
+__device__ __forceinline__ float lens_radius(const TraceParams& p, bool parent) {
+    if (!(p.defocus_angle > 0.0f)) return 0.0f;
+    const v3 du = mk(p.ddu[0], p.ddu[1], p.ddu[2]), dv = mk(p.ddv[0], p.ddv[1], p.ddv[2]);
+    const float a = dot(du, du), b = dot(dv, dv), c = dot(du, dv);
+    if (parent) return __builtin_amdgcn_sqrtf(a + b);
+    const float h = 0.5f * (a + b), g = 0.5f * (a - b);
+    return __builtin_amdgcn_sqrtf(h + __builtin_amdgcn_sqrtf(fmaf(g, g, c * c))) * 1.0001f;
+}
+
+// The bundle of a tile's camera rays, for the list build: rho(t) = r_o + the largest of
+// sin_t t, -sin_n t and -sin_t t - 2 r_o (far, near, back above).
+struct Beam {
+    v3 apex, axis;          // Pc and the unit vector from the camera centre to it
+    float cos_t, sin_t;     // the far slope, also the directions' half-angle
+    float sin_n;            // the near slope: growth towards the lens (negative: a narrowing)
+    float r_o, d_max;       // r_q; a bound on |d| of every ray
+};
+
+// The beam of the camera rays through the focus-plane rectangle of pixel columns [x0, x1)
+// and rows [y0, y1) (one tile: 8 x 8).  parent: the single cone (sin_n = sin_t, the slope
+// taken against L - r_l - r_q, the lens radius sqrt(|ddu|^2 + |ddv|^2)), whose tests
+// evaluate to the bits they had.
+__device__ __forceinline__ bool footprint_beam(const TraceParams& p, float x0, float x1,
+                                               float y0, float y1, bool parent, Beam& k) {
     const v3 vul = mk(p.vul[0], p.vul[1], p.vul[2]), pdu = mk(p.pdu[0], p.pdu[1], p.pdu[2]),
              pdv = mk(p.pdv[0], p.pdv[1], p.pdv[2]);
     const v3 ctr = mk(p.center[0], p.center[1], p.center[2]);
@@ -738,11 +796,7 @@ __device__ __forceinline__ bool footprint_cone(const TraceParams& p, float x0, f
         const v3 q = fmas(c & 2 ? y1 : y0, pdv, fmas(c & 1 ? x1 : x0, pdu, vul));
         rq = fmaxf(rq, len3(sub(q, pc)));
     }
-    float rl = 0.0f;
-    if (p.defocus_angle > 0.0f) {
-        const v3 du = mk(p.ddu[0], p.ddu[1], p.ddu[2]), dv = mk(p.ddv[0], p.ddv[1], p.ddv[2]);
-        rl = __builtin_amdgcn_sqrtf(dot(du, du) + dot(dv, dv));
-    }
+    float rl = lens_radius(p, parent);
     const float mag = fabsf(pc.x) + fabsf(pc.y) + fabsf(pc.z) + fabsf(ctr.x) + fabsf(ctr.y) +
                       fabsf(ctr.z);
     rq = rq * 1.001f + 1e-5f * mag;                 // f32 evaluation of pc and o = pc - d + d
@@ -752,11 +806,39 @@ __device__ __forceinline__ bool footprint_cone(const TraceParams& p, float x0, f
     if (!(L > 4.0f * delta) || !__builtin_isfinite(L + mag)) return false;
     k.axis = mk(w.x / L, w.y / L, w.z / L);
     k.apex = pc;
-    k.sin_t = delta / (L - delta) * 1.01f;
+    if (parent) {
+        k.sin_t = delta / (L - delta) * 1.01f;
+        k.sin_n = k.sin_t;
+    } else {
+        k.sin_t = delta / L * 1.01f;
+        const float sn = (rl - rq) / L;
+        k.sin_n = sn * (sn > 0.0f ? 1.01f : 0.99f);
+    }
     k.cos_t = __builtin_amdgcn_sqrtf(1.0f - k.sin_t * k.sin_t) * 0.999f;
     k.r_o = rq;
     k.d_max = (L + delta) * 1.001f;
     return true;
+}
+
+// rho(t) - r_o: how far the beam has spread at t along the axis from the apex.  (A NaN or
+// infinite t leaves a NaN or +inf here, whatever the slopes' signs: the tests then keep.)
+__device__ __forceinline__ float beam_spread(const Beam& k, float t) {
+    return fmaxf(fmaxf(k.sin_t * t, -k.sin_n * t), fmaf(-k.sin_t, t, -2.0f * k.r_o));
+}
+
+// cone_misses() for the list build: true when sphere record g = (center, r*r) provably misses
+// every ray of the beam.  lhs is p cos - rho(t) above, less 1e-5 of the magnitudes for its own
+// f32 evaluation; R, m and the comparison are cone_misses' (|oc| <= |t| + p + r_o + d_max holds
+// for the beam as for the cone: C to the apex, the apex to q, q to o).
+__device__ __forceinline__ bool beam_misses(const Beam& k, float4 g) {
+    const v3 v = mk(g.x - k.apex.x, g.y - k.apex.y, g.z - k.apex.z);
+    const float t = dot(v, k.axis);
+    const float p = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-t, t, dot(v, v)), 0.0f));
+    const float at = fabsf(t), R = __builtin_amdgcn_sqrtf(g.w) * 1.0001f;
+    const float mag = at + p + k.r_o;
+    const float lhs = fmaf(p, k.cos_t, -beam_spread(k, t)) - k.r_o - 1e-5f * mag;
+    const float m = 2.5e-3f * (mag + k.d_max + R);
+    return lhs > R && lhs * lhs > fmaf(R, R, m * m) * 1.0001f;   // NaN anywhere -> keep
 }
 
 struct Cam {

@@ -165,6 +165,22 @@ _SIGS_CERTAIN = {
     "rt_certain_tiles_stats": (ctypes.c_int, [P, P]),
 }
 
+# include/rt_tile_lists.h
+_SIGS_TILE_LISTS = {
+    "rt_tile_lists": (ctypes.c_int, [P, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_set_tight_bundle": (ctypes.c_int, [P, ctypes.c_int]),
+}
+RT_TILE_LIST_MAX = 19
+RT_TILE_LIST_NONE = 0xFFFFFFFF
+RT_TILE_CERTAIN = 1
+
+
+class TileListC(ctypes.Structure):
+    """rt_tile_list (rt_tile_lists.h)."""
+    _fields_ = [("count", U32), ("removed", U32), ("flags", U32), ("reserved", U32),
+                ("records", (ctypes.c_float * 4) * RT_TILE_LIST_MAX)]
+
+
 # include/rt_selftest_roots.h
 _SIGS_SELFTEST_ROOTS = {
     "rt_selftest_roots": (ctypes.c_int, [P, ctypes.c_uint64, P]),
@@ -415,7 +431,8 @@ def lib() -> ctypes.CDLL:
                                   **_SIGS_AOV, **_SIGS_DENOISE, **_SIGS_REPROJECT,
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
                                   **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION,
-                                  **_SIGS_MATTE, **_SIGS_QUERY, **_SIGS_CERTAIN}.items():
+                                  **_SIGS_MATTE, **_SIGS_QUERY, **_SIGS_CERTAIN,
+                                  **_SIGS_TILE_LISTS}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -466,6 +483,10 @@ def occlusion_symbols() -> list[str]:
 
 def certain_symbols() -> list[str]:
     return list(_SIGS_CERTAIN)
+
+
+def tile_lists_symbols() -> list[str]:
+    return list(_SIGS_TILE_LISTS)
 
 
 def selftest_roots_symbols() -> list[str]:

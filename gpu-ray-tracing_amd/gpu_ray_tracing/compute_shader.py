@@ -260,6 +260,26 @@ class ComputeShaderPipeline:
             _lib.call("rt_certain_tiles_stats", self._ctx, out)
         return {"certain_tiles": int(out[0]), "certain_pairs": int(out[1])}
 
+    def set_tight_bundle(self, on: bool) -> None:
+        """rt_set_tight_bundle: whether the lists are built against the two-slope beam of a
+        tile's camera rays (default on) or the single cone used before it; identical pixels."""
+        if hasattr(_lib.lib(), "rt_set_tight_bundle"):        # (absent from older builds)
+            _lib.call("rt_set_tight_bundle", self._ctx, 1 if on else 0)
+
+    def tile_lists(self) -> dict:
+        """rt_tile_lists: the candidate lists built last, copied to the host — per tile (local
+        band by local band, (width + 7) // 8 tiles each) "count" (RT_TILE_LIST_NONE: no list),
+        "removed", "flags" (u32 arrays) and "records" (tiles x 19 x 4 f32: centre and radius
+        squared of entry j < count, zero beyond)."""
+        n = ctypes.c_uint64(0)
+        _lib.call("rt_tile_lists", self._ctx, None, 0, ctypes.byref(n))
+        buf = np.zeros((int(n.value), 4 + 4 * _lib.RT_TILE_LIST_MAX), np.uint32)
+        assert buf.shape[1] * buf.itemsize == ctypes.sizeof(_lib.TileListC)
+        if n.value:
+            _lib.call("rt_tile_lists", self._ctx, buf.ctypes.data, n.value, ctypes.byref(n))
+        return {"count": buf[:, 0].copy(), "removed": buf[:, 1].copy(), "flags": buf[:, 2].copy(),
+                "records": buf[:, 4:].copy().view(np.float32).reshape(-1, _lib.RT_TILE_LIST_MAX, 4)}
+
     def set_update_submit(self, mode: str) -> None:
         """rt_set_update_submit: how update_frames submits one-frame updates — "auto" (HIP
         launches; AQL is opt-in), "hip" or "aql" (AQL packets on the context's own HSA
