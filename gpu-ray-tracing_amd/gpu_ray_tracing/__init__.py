@@ -8,7 +8,8 @@ importing this package does not load it; the first call does, and raises if it i
 from . import _lib
 from .camera import CameraSettings, SceneCamera
 from . import image_io
-from .compute_shader import (ADAPTIVE_DEFAULTS, DENOISE_DEFAULTS, EDIT_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS, RT_STRIPE_ROWS,
+from .compute_shader import (ADAPTIVE_DEFAULTS, DENOISE_DEFAULTS, EDIT_DEFAULTS, GUIDED_DEFAULTS, REPROJECT_DEFAULTS,
+                             RESIZE_FILL_NEAREST, RESIZE_FILL_NONE, RT_STRIPE_ROWS,
                              ComputeShaderImages, ComputeShaderNode,
                              ComputeShaderPipeline, chain_schedule, edit_plan, partition_bands,
                              reproject_basis, srgb_thresholds,
@@ -44,5 +45,5 @@ __all__ = [
     "DENOISE_DEFAULTS", "RT_DENOISE_MAX_ITERATIONS", "REPROJECT_DEFAULTS", "reproject_basis",
     "GUIDED_DEFAULTS", "RT_VARIANCE_MAX_ITERATIONS", "ADAPTIVE_DEFAULTS",
     "EDIT_DEFAULTS", "edit_plan", "RT_EDIT_NONE", "RT_EDIT_MOVED", "RT_EDIT_MAX_BALLS",
-    "RT_MATTE_SLOTS", "QUERY_ROUTES",
+    "RT_MATTE_SLOTS", "QUERY_ROUTES", "RESIZE_FILL_NONE", "RESIZE_FILL_NEAREST",
 ]

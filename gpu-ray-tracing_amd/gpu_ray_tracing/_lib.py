@@ -243,6 +243,26 @@ class ReprojectPlanesC(ctypes.Structure):
                 ("normal", P), ("material", P)]
 
 
+# include/rt_resize.h (carrying the accumulator across image sizes)
+_SIGS_RESIZE = {
+    "rt_resize_params_default": (None, [P]),
+    "rt_resize_carry": (ctypes.c_int, [P, P, U32, U32, U32, U32, P, P, P, P, P]),
+}
+RT_RESIZE_FILL_NONE = 0
+RT_RESIZE_FILL_NEAREST = 1
+
+
+class ResizeParamsC(ctypes.Structure):
+    """rt_resize_params (rt_resize.h), 32 bytes."""
+    _fields_ = [("max_history", U32), ("lambertian_only", U32), ("position_tolerance2", F),
+                ("sky", U32), ("fill", U32), ("_reserved", U32 * 3)]
+
+
+class ResizeImagesC(ctypes.Structure):
+    """rt_resize_images (rt_resize.h): device pointers, 32 bytes."""
+    _fields_ = [("prev_rgba", P), ("dst_rgba", P), ("prev_second", P), ("dst_second", P)]
+
+
 # include/rt_variance.h (luminance moments and the variance-guided filter)
 _SIGS_VARIANCE = {
     "rt_variance_filter_params_default": (None, [P]),
@@ -432,7 +452,7 @@ def lib() -> ctypes.CDLL:
                                   **_SIGS_VARIANCE, **_SIGS_ADAPTIVE, **_SIGS_CONVERGE,
                                   **_SIGS_PROGRESS, **_SIGS_EDIT, **_SIGS_OCCLUSION,
                                   **_SIGS_MATTE, **_SIGS_QUERY, **_SIGS_CERTAIN,
-                                  **_SIGS_TILE_LISTS}.items():
+                                  **_SIGS_TILE_LISTS, **_SIGS_RESIZE}.items():
             if "RT_HIP_LIB" in os.environ and not hasattr(handle, name):
                 continue  # an older experiment build (tools/ab_variants.py)
             fn = getattr(handle, name)
@@ -503,6 +523,10 @@ def denoise_symbols() -> list[str]:
 
 def reproject_symbols() -> list[str]:
     return list(_SIGS_REPROJECT)
+
+
+def resize_symbols() -> list[str]:
+    return list(_SIGS_RESIZE)
 
 
 def variance_symbols() -> list[str]:

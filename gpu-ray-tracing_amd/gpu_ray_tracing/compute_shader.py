@@ -33,6 +33,11 @@ DENOISE_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_color": 1.0,
 REPROJECT_DEFAULTS = {"max_history": 64, "position_tolerance2": 1e-5, "lambertian_only": True}
 
 
+# ComputeShaderPipeline.resize_carry's `fill`: rt_resize.h's RT_RESIZE_FILL_*
+RESIZE_FILL_NONE = _lib.RT_RESIZE_FILL_NONE
+RESIZE_FILL_NEAREST = _lib.RT_RESIZE_FILL_NEAREST
+
+
 # ComputeShaderPipeline.denoise_guided's defaults: rt_variance_filter_params_default's
 GUIDED_DEFAULTS = {"iterations": 5, "normal_power_log2": 5, "sigma_luminance": 1.0,
                    "sigma_position": 0.5, "min_history": 4, "fallback_variance": 1.0}
@@ -937,6 +942,102 @@ class ComputeShaderPipeline:
         _lib.call("rt_reproject", self._ctx, _ptr(prev_image), _ptr(out), width, height,
                   ctypes.byref(cam), ctypes.byref(c), ctypes.byref(params), self._stream())
         return out
+
+    # ---- carrying across image sizes (rt_resize.h) ---------------------------------------
+    def resize_carry(self, prev_image: torch.Tensor, prev_size, size,
+                     prev_camera: SceneCamera, camera: SceneCamera | None,
+                     prev_guides: dict, guides: dict, *,
+                     max_history: int = REPROJECT_DEFAULTS["max_history"],
+                     position_tolerance2: float = REPROJECT_DEFAULTS["position_tolerance2"],
+                     lambertian_only: bool = REPROJECT_DEFAULTS["lambertian_only"],
+                     sky: bool = False, fill: int = RESIZE_FILL_NONE,
+                     prev_second: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, out_second: torch.Tensor | None = None):
+        """rt_resize_carry: `reproject` from a previous view of prev_size = (width, height)
+        into a current view of size = (width, height).  prev_guides are trace_aov's
+        "sphere_id" and "hit" at the previous size, guides its "sphere_id", "hit", "normal"
+        and, with lambertian_only, "material" at the current size.  With `sky` a pixel whose
+        ray misses carries the previous sky pixels in its direction; with fill =
+        RESIZE_FILL_NEAREST a pixel that gets no history shows the nearest previous texel's
+        colour with a sample count of 0 (a restart for update).  `camera`, the current view's,
+        is needed for either and may be None otherwise.  prev_second (a moments image, say) is
+        carried by the same rules in the same launch into out_second.  Returns `out`
+        (allocated when not given), or (out, out_second) with prev_second.  Every bit equals
+        the NumPy restatement in tests/test_resize.py.  Enqueued on torch's current stream."""
+        (pw, ph), (width, height) = (int(v) for v in prev_size), (int(v) for v in size)
+        need, prev_need = width * height * 4, pw * ph * 4
+
+        def image_like(t, what, dtype=torch.float32, n=need):
+            if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype
+                    or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous CUDA (HIP) {dtype} tensor of at "
+                                 f"least {n} elements")
+            return t
+
+        image_like(prev_image, "prev_image", n=prev_need)
+        if out_second is not None and prev_second is None:
+            raise ValueError("out_second is given without prev_second")
+        if (sky or fill) and camera is None:
+            raise ValueError("sky and fill need the current view's camera")
+        names = ("sphere_id", "hit", "normal") + (("material",) if lambertian_only else ())
+        missing = [f"prev_guides[{k!r}]" for k in ("sphere_id", "hit")
+                   if prev_guides.get(k) is None]
+        missing += [f"guides[{k!r}]" for k in names if guides.get(k) is None]
+        if missing:
+            raise ValueError(f"missing {missing} (the planes of trace_aov)")
+        c = _lib.ReprojectPlanesC()
+        for field, src, k in [("prev_sphere_id", prev_guides, "sphere_id"),
+                              ("prev_hit", prev_guides, "hit")] + \
+                             [(k, guides, k) for k in names]:
+            is_id = k == "sphere_id"
+            is_prev = src is prev_guides
+            what = ("prev_guides" if is_prev else "guides") + f"[{k!r}]"
+            texels = pw * ph if is_prev else width * height
+            t = image_like(src[k], what, torch.int32 if is_id else torch.float32,
+                           texels if is_id else 4 * texels)
+            setattr(c, field, t.data_ptr())
+        if out is None:
+            out = torch.empty((height, width, 4), dtype=torch.float32, device=self.torch_device)
+        image_like(out, "out")
+        images = _lib.ResizeImagesC(prev_image.data_ptr(), out.data_ptr(), None, None)
+        if prev_second is not None:
+            image_like(prev_second, "prev_second", n=prev_need)
+            if out_second is None:
+                out_second = torch.empty((height, width, 4), dtype=torch.float32,
+                                         device=self.torch_device)
+            image_like(out_second, "out_second")
+            images.prev_second, images.dst_second = prev_second.data_ptr(), out_second.data_ptr()
+        params = _lib.ResizeParamsC(int(max_history), 1 if lambertian_only else 0,
+                                    float(position_tolerance2), 1 if sky else 0, int(fill))
+        prev_cam = prev_camera.to_c()
+        cam = camera.to_c() if camera is not None else None
+        _lib.call("rt_resize_carry", self._ctx, ctypes.byref(images), pw, ph, width, height,
+                  ctypes.byref(prev_cam), ctypes.byref(cam) if cam is not None else None,
+                  ctypes.byref(c), ctypes.byref(params), self._stream())
+        return out if prev_second is None else (out, out_second)
+
+    def upscale(self, image: torch.Tensor, size_small, size, camera_small: SceneCamera,
+                camera: SceneCamera, guides_small: dict | None = None,
+                guides: dict | None = None, *, spheres: SphereCollection | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+        """A size-sized picture of the accumulator `image` rendered at size_small (both
+        (width, height)) for the view camera_small, as seen by `camera`: resize_carry with
+        lambertian_only off, sky on and fill = RESIZE_FILL_NEAREST, so that every pixel shows a
+        colour and the full-size G-buffer places every silhouette.  Whichever of guides_small /
+        guides is not given is traced with trace_aov over `spheres`, the current scene, which
+        is required then (the pipeline does not guess it from an earlier call).  Returns the
+        full-size image (`out` when given), ready for `present`."""
+        if (guides_small is None or guides is None) and spheres is None:
+            raise ValueError("spheres is needed to trace the guides that are not given")
+        if guides_small is None:
+            guides_small = self.trace_aov(int(size_small[0]), int(size_small[1]), camera_small,
+                                          spheres, planes=("sphere_id", "hit"))
+        if guides is None:
+            guides = self.trace_aov(int(size[0]), int(size[1]), camera, spheres,
+                                    planes=("sphere_id", "hit", "normal"))
+        return self.resize_carry(image, size_small, size, camera_small, camera, guides_small,
+                                 guides, lambertian_only=False, sky=True,
+                                 fill=RESIZE_FILL_NEAREST, out=out)
 
     # ---- carrying across scene edits (rt_scene_edit.h) -----------------------------------
     def carry_edit(self, prev_image: torch.Tensor, width: int, height: int,
